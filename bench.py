@@ -15,8 +15,11 @@ class-balanced sample of it is timed (computed@rate0, skipped, computed@rate1) a
 12*t(computed@rate0) + 11*t(computed@rate1) + 27*t(skipped) -- the JSON says which.
 
 One JSON line on rank 0, with `roofline` (block-sparse attention kernel: algorithmic FLOPs of the realised masks /
-launch durations measured with HIP events on the launch stream) and `cpu_baseline` (the oracle's AttenCarve op timed
-on the host cores on a bounded sample and extrapolated by kept block pairs; attention only).
+launch durations measured with HIP events on the launch stream).  A plain run sets up, warms up, times the steps and
+prints that line; --full adds the legs that take runs of their own behind the timed region: `dense_reference`,
+`extra.attn_other_kernel`, `roofline.traffic` read by counter passes, `roofline_secondary`, `extra.wan14b`,
+`roofline_xgmi` (N > 1) and `cpu_baseline` (the oracle's AttenCarve op timed on the host cores on a bounded sample and
+extrapolated by kept block pairs; attention only).  --dump-outputs DIR writes the last timed step's output latents.
 """
 import argparse
 import json
@@ -48,6 +51,7 @@ PRESETS = {   # scripts/hyvideo_jenga_{base,turbo,flash,3stage}.sh and scripts/h
 
 from benchlib.consts import ATTN_ALGORITHMIC_BYTES, FLOPS_PER_PAIR, HBM_PEAK_GBPS, MFMA_PEAK_TFLOPS, PMC_FILE, attn_kernel_name  # noqa: E402,F401
 from benchlib.cpu_ref import cpu_baseline  # noqa: E402
+from benchlib.dump import DUMP_CAP_BYTES, dump_outputs  # noqa: E402,F401
 from benchlib.launch import _flush_c_stdio, _free_port, _StdoutToStderr, launch_command  # noqa: E402,F401
 from benchlib.pmc import _apply_pmc, pmc_read_in_this_run, traffic_bytes_per_pair  # noqa: E402
 from benchlib.power import PowerSampler, _host_cpu  # noqa: E402,F401
@@ -60,6 +64,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs behind the timed region (dense reference, the other attention kernel, the in-run "
+                         "counter passes, roofline_secondary, the Wan2.1-14B leg, roofline_xgmi for N > 1, cpu_baseline); each "
+                         "keeps its --no-* switch.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last of them returned (the DiT's output latents) as DIR/<name>.npy "
+                         "in float32 (rank 0; a fixed seeded sample when it exceeds 64 MB): the inputs are seeded, so two builds "
+                         "can be compared output for output")
     ap.add_argument("--rates", type=float, nargs="+", default=None,
                     help="sa-drop-rates per stage; default per preset (base: 0.7 0.8 = BASELINE.json configs[1]; "
                          "0.75 0.85 = the shipped scripts/hyvideo_jenga_base.sh)")
@@ -438,13 +450,15 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     finite = bool(torch.isfinite(out.float()).all().item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"latents_out": out})      # before any later leg can reuse the buffer
 
     extras_failed = {}      # legs behind the timed region that raised: reported in the line, never fatal
     # ---- the un-accelerated model beside it (NOT in the timed region): ONE computed step with sa-drop 0 at the final
     #      resolution, no skipping; its loop is 50 such steps (README.md:80-82: 1625 s dense vs 310 s Jenga-Base)
     try:
         dense_ms = None
-        if not a.no_dense_ref and a.preset != "dense":
+        if a.full and not a.no_dense_ref and a.preset != "dense":
             from jenga_amd.modules import attention as _att
             st = stages[-1]
             if not dist_on and sim <= 1:
@@ -474,7 +488,7 @@ def main():
     #      kernel that is not the default (pair kernel <-> LP kernel), same box, same lists
     try:
         rot_ms, rot_prof, other_flags = {}, None, None
-        if not a.no_other_kernel_ref and not dist_on and sim <= 1 and a.preset != "dense" and \
+        if a.full and not a.no_other_kernel_ref and not dist_on and sim <= 1 and a.preset != "dense" and \
                 (_capi.ATTN_DEFAULT_FLAGS & (_capi.ATTN_LP | _capi.ATTN_PAIR)):
             flags0 = _capi.ATTN_DEFAULT_FLAGS
             other_flags = _capi.ATTN_LP_FLAGS if (flags0 & _capi.ATTN_PAIR) else _capi.ATTN_PAIR_FLAGS
@@ -502,7 +516,7 @@ def main():
     #      212-217 (6 all-to-alls per layer); here per layer: Q|K, V, O all-to-alls + the text all-gather (ulysses.py)
     try:
         xgmi_raw = None
-        if dist_on and not a.no_xgmi_extras and a.preset != "dense":
+        if a.full and dist_on and not a.no_xgmi_extras and a.preset != "dense":
             sp_blocks = [b for b in list(model.double_blocks) + list(model.single_blocks) if b.hybrid_seq_parallel_attn]
             ex0 = sp_blocks[0].hybrid_seq_parallel_attn.exchange()
             Hh_, D_ = model.heads_num, 128
@@ -654,7 +668,7 @@ def main():
     traffic_provenance = ("derived, not read in this run: committed per-kept-pair constants (one per drop "
                           "rate) x this run's pairs, launch by launch")
     pmc_note = None
-    want_pmc = a.pmc == "on" or (a.pmc == "auto" and not dist_on and sim <= 1 and a.preset != "dense" and rank == 0)
+    want_pmc = a.full and (a.pmc == "on" or (a.pmc == "auto" and not dist_on and sim <= 1 and a.preset != "dense" and rank == 0))
     if want_pmc and ps["launches"] > 0:
         child_argv = ["--preset", a.preset, "--rates"] + [str(r_) for r_ in a.rates] + [
             "--p-remain", str(a.p_remain), "--latent"] + [str(v_) for v_ in a.latent] + [
@@ -839,7 +853,7 @@ def main():
                     "final resolution, measured after the timed region; the dense loop computes all 50 steps "
                     "(no step skipping).  The reference's own ratio on H800: 1625 s / 310 s = 5.24 (README.md:80-82)"}
     n_layers = len(model.double_blocks) + len(model.single_blocks)
-    if rank == 0 and not dist_on and sim <= 1 and not a.no_secondary:
+    if a.full and rank == 0 and not dist_on and sim <= 1 and not a.no_secondary:
         st = stages[-1]
         try:
             res["roofline_secondary"] = secondary_roofline(
@@ -847,7 +861,7 @@ def main():
                 p_remain=a.p_remain, nbm=st["curve"][0][2])
         except Exception as e:      # noqa: BLE001
             extras_failed["roofline_secondary"] = repr(e)[:300]
-    if rank == 0 and not dist_on and sim <= 1 and not a.no_wan_extra and a.preset == "base" and not a.depth:
+    if a.full and rank == 0 and not dist_on and sim <= 1 and not a.no_wan_extra and a.preset == "base" and not a.depth:
         del model
         torch.cuda.empty_cache()
         try:
@@ -855,7 +869,7 @@ def main():
         except Exception as e:      # noqa: BLE001
             extras_failed["wan14b"] = repr(e)[:300]
     cb = None
-    if rank == 0 and not dist_on and not a.no_cpu_baseline:
+    if a.full and rank == 0 and not dist_on and not a.no_cpu_baseline:
         try:
             cb = cpu_baseline(a.rates, a.p_remain)
         except Exception as e:      # noqa: BLE001

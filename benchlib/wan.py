@@ -11,6 +11,7 @@ from .consts import ATTN_ALGORITHMIC_BYTES, FLOPS_PER_PAIR, HBM_PEAK_GBPS, MFMA_
 
 
 from .cpu_ref import cpu_baseline
+from .dump import dump_outputs
 from .power import PowerSampler
 
 
@@ -102,6 +103,8 @@ def wan_main(a, dev):
     pw = power.stop()
     _capi.ATTN_PROFILE = None
     finite = bool(torch.isfinite(y).all().item())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"latents_out": y})
     cls = {}
     for r, e0, e1 in evs:
         cls.setdefault(r, []).append(e0.elapsed_time(e1))
@@ -152,7 +155,7 @@ def wan_main(a, dev):
                  "frac_of_mfma_peak": round((flops + gemm + cross) / max(elapsed, 1e-9) / 1e12 / MFMA_PEAK_TFLOPS, 4)},
         "power": pw,
     }
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         cb = cpu_baseline(rates2, p_remain, workload="wan14b")
         res["cpu_baseline"] = {
             "value": round(cb["s_per_layer"] * cfg["num_layers"] * 100, 1), "unit": "s/video", "cores": cb["cores"],

@@ -160,5 +160,35 @@ def test_bench_and_its_helper_modules_reference_no_undefined_global():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import check_names
     for m in ("bench", "benchlib.consts", "benchlib.pmc", "benchlib.launch", "benchlib.power", "benchlib.secondary",
-              "benchlib.cpu_ref", "benchlib.wan"):
+              "benchlib.cpu_ref", "benchlib.wan", "benchlib.dump"):
         assert check_names.undefined_globals(m) == [], m
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs no leg behind the timed region: --full is off unless given."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 3, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d" and a.no_cpu_baseline is True
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample_over_the_cap(tmp_path):
+    import numpy as np
+    import torch
+
+    import bench
+    x = torch.arange(2 * 3 * 50, dtype=torch.float32).reshape(2, 3, 50).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "a"), {"latents_out": x})
+    got = np.load(tmp_path / "a" / "latents_out.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 3, 50) and np.array_equal(got, x.float().numpy())
+    # over the cap: the same 25 sorted positions of the flattened output in every run
+    y = torch.arange(300, dtype=torch.float64).reshape(6, 50)       # (every element is its own flat position)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"latents_out": y}, cap_bytes=100)
+    b, c = np.load(tmp_path / "b" / "latents_out.npy"), np.load(tmp_path / "c" / "latents_out.npy")
+    assert b.dtype == np.float32 and b.shape == (25,) and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and b.min() >= 0 and b.max() < 300 and np.array_equal(b, np.round(b))
+    assert bench.DUMP_CAP_BYTES <= 64 * 10 ** 6

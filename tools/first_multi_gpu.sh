@@ -47,7 +47,7 @@ for P in "base-mgpu" "turbo-mgpu" "3stage-mgpu --i2v"; do
     for N in $NS; do
       F="$OUT/bench_${TAG}_${MODE}_n$N"
       # (python bench.py --gpus N launches itself under torch.distributed.run, one rank per GPU, rendezvous on 127.0.0.1)
-      JENGA_ULYSSES_EXCHANGE=$MODE timeout 3600 python bench.py --gpus $N --preset $P $STEPS --no-cpu-baseline --no-wan-extra \
+      JENGA_ULYSSES_EXCHANGE=$MODE timeout 3600 python bench.py --full --gpus $N --preset $P $STEPS --no-cpu-baseline --no-wan-extra \
         > "$F.json" 2> "$F.err" || FAILED="$FAILED bench_${TAG}_${MODE}_n$N"
       tail -c 300 "$F.json" | tr '\n' ' ' | cut -c1-160; echo
     done
