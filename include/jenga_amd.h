@@ -351,6 +351,26 @@ int jenga_cross_attn_fwd(void* stream, const void* q, const void* k, const void*
                          float sm_scale, int dtype);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Dense variable-length attention (csrc/dattn.hip).  Replaces the reference's dense call, flash_attn_varlen_func over
+ * cu_seqlens (hyvideo/modules/attenion.py:108-121), in ONE launch: no kept-block lists, no jenga_pack_v workspace, any
+ * segment boundaries.  (An additive export inside ABI 4: callers that bind it against an older library of the same number fail
+ * at symbol lookup, as jenga_amd/_capi.py does.)
+ *   q [Tq, H, 128], k / v [Tk, H, 128], o like q: packed tokens with a row (`_ss`) and a head (`_sh`) stride in elements, both
+ *   multiples of 8, 16-byte aligned pointers.  cu_seqlens_q / cu_seqlens_kv: int32 [n_segments + 1] ON THE DEVICE, non-decreasing,
+ *   starting at 0, any boundaries (nothing needs to be aligned; zero-length segments are fine), cu_seqlens_q[n] <= Tq,
+ *   cu_seqlens_kv[n] <= Tk.  The host never reads them: the grid is (ceil(Tq / 256) + n_segments) * H workgroups, each finds
+ *   its (segment, 256-row query tile) by binary search, the surplus exits; values outside [0, Tq] / [0, Tk] are clamped there.
+ *   Query rows of segment i attend to exactly the keys of segment i: o = softmax(q.k^T * sm_scale) . v with fp32 scores scaled
+ *   in fp32 (exp2 domain), online softmax, P rounded to dtype before P.V, the row sum taken from the unrounded p, fp32
+ *   accumulation, one rounding of o.  Rows of a segment without keys and rows >= cu_seqlens_q[n] are written as zeros.
+ *   sm_scale > 0.  Tk * (row stride of k / v) * 2 bytes must stay below 4 GiB.  Deterministic; close to, not bit-equal with,
+ *   jenga_bsattn_fwd on the same problem (that kernel rounds a pre-scaled q to dtype). */
+int jenga_dense_varlen_fwd(void* stream, const void* q, const void* k, const void* v, void* o,
+                           const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_kv, int64_t n_segments, int64_t Tq,
+                           int64_t Tk, int64_t H, int64_t q_ss, int64_t q_sh, int64_t k_ss, int64_t k_sh, int64_t v_ss,
+                           int64_t v_sh, int64_t o_ss, int64_t o_sh, float sm_scale, int dtype);
+
+/* ---------------------------------------------------------------------------------------------------
  * Ulysses head pack/unpack: the local halves of xFuserLongContextAttention.forward's SeqAllToAll4D calls
  * (hyvideo/modules/xdit_ring_atten.py:118-131 scatter heads / gather sequence, :212-217 the reverse).
  * The exchange itself is one RCCL all_to_all_single issued from the host (torch.distributed); these

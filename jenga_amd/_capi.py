@@ -60,6 +60,7 @@ SIGNATURES = {
     "jenga_ulysses_unpack_heads": (_i32, [_vp, _vp, _vp] + [_i64] * 7),
     "jenga_stream_delay": (_i32, [_vp, ctypes.c_double]),
     "jenga_cross_attn_fwd": (_i32, [_vp] * 5 + [_i64] * 14 + [_f32, _i32]),
+    "jenga_dense_varlen_fwd": (_i32, [_vp] * 7 + [_i64] * 12 + [_f32, _i32]),
     "jenga_linear_export_choices": (_i64, [_vp, _i64]),
     "jenga_linear_import_choices": (_i32, [_vp, _i64]),
     "jenga_linear_import_mismatches": (_i64, []),
@@ -796,6 +797,38 @@ def cross_attn_fwd(q, k, v, sm_scale=None, out=None, kv_len=None):
                                           kv_len, *_bshd_strides(q), *_bshd_strides(k), *_bshd_strides(out),
                                           float(D ** -0.5 if sm_scale is None else sm_scale), dtype_code(q.dtype)),
                "jenga_cross_attn_fwd")
+    return out
+
+
+def dense_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_kv=None, sm_scale=None, out=None):
+    """Dense variable-length attention in one launch (csrc/dattn.hip; flash_attn_varlen_func, attenion.py:108-121): q [Tq,H,128],
+    k / v [Tk,H,128] packed tokens (unit head_dim stride), cu_seqlens_* int32 [n+1] on q's device (kv defaults to q's).  Query rows
+    of segment i attend to the keys of segment i; rows >= cu_seqlens_q[-1] and rows of a segment without keys come back as
+    zeros.  Nothing is read back from the device: the call can be captured in a graph."""
+    _need_gpu(q, "dense_varlen_fwd")
+    if cu_seqlens_kv is None:
+        cu_seqlens_kv = cu_seqlens_q
+    if q.dim() != 3 or q.shape[2] != 128 or k.dim() != 3 or tuple(k.shape[1:]) != tuple(q.shape[1:]) or v.shape != k.shape \
+            or k.dtype != q.dtype or v.dtype != q.dtype or q.shape[0] == 0:
+        raise ValueError("dense_varlen_fwd: q [Tq,H,128], k / v [Tk,H,128] of one dtype, Tq >= 1")
+    for name, c in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_kv", cu_seqlens_kv)):
+        if c.dtype != torch.int32 or c.dim() != 1 or c.device != q.device or not c.is_contiguous():
+            raise ValueError(f"dense_varlen_fwd: {name} must be a contiguous int32 vector on q's device (it is never read on "
+                             "the host)")
+    if cu_seqlens_kv.numel() != cu_seqlens_q.numel() or cu_seqlens_q.numel() < 2:
+        raise ValueError("dense_varlen_fwd: cu_seqlens_q and cu_seqlens_kv must have the same length n + 1 >= 2")
+    q, k, v = (t if t.stride(2) == 1 else t.contiguous() for t in (q, k, v))
+    if out is None:
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    elif out.shape != q.shape or out.dtype != q.dtype or out.stride(2) != 1 or out.device != q.device:
+        raise ValueError("dense_varlen_fwd: out must match q (unit head_dim stride)")
+    Tq, H, D = q.shape
+    with _on(q.device):
+        _check(lib().jenga_dense_varlen_fwd(_stream(q.device), _p(q), _p(k), _p(v), _p(out), _p(cu_seqlens_q),
+                                            _p(cu_seqlens_kv), cu_seqlens_q.numel() - 1, Tq, k.shape[0], H, q.stride(0),
+                                            q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0),
+                                            out.stride(1), float(D ** -0.5 if sm_scale is None else sm_scale),
+                                            dtype_code(q.dtype)), "jenga_dense_varlen_fwd")
     return out
 
 

@@ -40,6 +40,8 @@ SOURCES = [
     ("bsattn3.hip", ["-fno-honor-nans", "-fno-slp-vectorize", "-Wno-inline-asm"]),
     # the pair kernel (round 5): same flags; its QK^T MFMAs are inline asm (lp_core.h, LP_QK_MFMA_ASM)
     ("bsattn5.hip", ["-fno-honor-nans", "-fno-slp-vectorize", "-Wno-inline-asm"]),
+    # the dense varlen kernel: the attention flags, and no packed fp32 by construction (NO_PK includes -fno-slp-vectorize)
+    ("dattn.hip", ["-fno-honor-nans", "-Wno-inline-asm"] + NO_PK),
 ]
 
 def _hipcc():

@@ -102,8 +102,25 @@ class UnsupportedAttentionArgument(NotImplementedError, ValueError):
     unknown mode, attenion.py:150.)"""
 
 
+def attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_kv=None, sm_scale=None, out=None):
+    """flash_attn_varlen_func (attenion.py:108-121) in one launch of the dense varlen kernel (_capi.dense_varlen_fwd): query rows
+    of segment i attend to the keys of segment i, softmax scale head_dim ** -0.5 unless given.  q / k / v: packed [T,H,128], or
+    [B,S,H,128] flattened over B * S the way the reference's cu_seqlens count tokens (get_cu_seqlens: sample b starts at
+    b * S); q and k / v may differ in length.  cu_seqlens_*: int32 [n+1] on the device with any boundaries; they are never read
+    on the host, so the call neither synchronises nor breaks a graph capture.  Rows behind the last boundary and rows of a
+    segment without keys are zeros.  Returns a tensor shaped like q."""
+    if q.dim() == 3:
+        return _capi.dense_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_kv, sm_scale, out)
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("attention_varlen: q / k / v must be [T,H,128] or [B,S,H,128]")
+    flat = lambda t: t.reshape(t.shape[0] * t.shape[1], t.shape[2], t.shape[3])   # a view wherever the strides allow one
+    o = _capi.dense_varlen_fwd(flat(q), flat(k), flat(v), cu_seqlens_q, cu_seqlens_kv, sm_scale,
+                               None if out is None else out.view(-1, out.shape[2], out.shape[3]))
+    return o.view(q.shape)
+
+
 def attention(q, k, v, mode="flash", drop_rate=0, attn_mask=None, causal=False, cu_seqlens_q=None,
-              cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None, batch_size=1):
+              cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None, batch_size=1, kernel="lists"):
     """Dense path taken when sa_drop_rate == 0 (attenion.py:60-157, mode "flash" = flash_attn_varlen_func over the
     (valid | padding) segments).  Runs the same HIP kernel with every kv block kept and the kv-length mask on, for all
     query blocks of the valid segment; the padding segment (text padding attending among itself) is one small dense call
@@ -114,7 +131,13 @@ def attention(q, k, v, mode="flash", drop_rate=0, attn_mask=None, causal=False, 
     semantics (a mask instead of cu_seqlens, [B,H,S,D] layout); they raise instead of silently running the flash semantics
     (VERDICT r5 missing 4).  In "flash" mode the reference itself drops attn_mask / causal / drop_rate on the floor
     (flash_attn_varlen_func is called without them, :108-116); a caller that passes them expects something this call does
-    not do, so they raise too."""
+    not do, so they raise too.
+
+    kernel: "lists" (default) is the path described above: batch 1, S a multiple of 128, the (valid | padding) pair.  "varlen"
+    hands the whole call to the dense varlen kernel (attention_varlen) in one launch over the cu_seqlens as given: any batch,
+    any S, any segments, no host read of cu_seqlens (graph-capturable).  Same semantics, not bit-equal with "lists"."""
+    if kernel not in ("lists", "varlen"):
+        raise ValueError(f"jenga_amd attention: kernel {kernel!r} is not one of \"lists\", \"varlen\"")
     if mode != "flash":
         raise UnsupportedAttentionArgument(f"jenga_amd attention: mode {mode!r} is not implemented (only \"flash\")")
     if attn_mask is not None:
@@ -125,6 +148,9 @@ def attention(q, k, v, mode="flash", drop_rate=0, attn_mask=None, causal=False, 
         raise UnsupportedAttentionArgument("jenga_amd attention: drop_rate != 0 is not supported (inference only)")
     if cu_seqlens_q is None:
         raise ValueError("jenga_amd attention: cu_seqlens_q is required (get_cu_seqlens)")
+    if kernel == "varlen":
+        o = attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_kv)
+        return o.reshape(q.shape[0], q.shape[1], -1)
     if q.shape[0] != 1:
         raise ValueError("jenga_amd dense attention: batch must be 1")
     B, S, H, D = q.shape

@@ -26,8 +26,66 @@ def timed(fn, iters, warmup=1):
     return e0.elapsed_time(e1) / iters, out
 
 
+DENSE_SHAPES = {   # name -> (image tokens, text tokens, valid text, heads)
+    "hunyuan_720p": (115200, 256, 64, 24),
+    "wan14b_720p": (75600, 48, 0, 40),     # 21 x 45 x 80 tokens, padded to 591 blocks by the Wan attention op
+}
+PEAK_BF16_TFLOPS, PEAK_HBM_TBPS = 2500.0, 8.0
+
+
+def dense_ab(a):
+    """--dense: the dense call of the product, old path against new path, same tensors, same process, alternating.
+    old: attention() as shipped -- jenga_pack_v + jenga_bsattn_fwd over the cached all-kept lists + padding_segment (the
+         one-time list build happens in the warm-up and is not timed; everything per call is);
+    new: attention(kernel="varlen") -- one jenga_dense_varlen_fwd launch.
+    Device events around `--iters` calls (choose it so that a window is >= 1 s), `--repeats` windows per path."""
+    from jenga_amd.modules.attention import attention
+    dev = torch.device("cuda:0")
+    record = {"peak_bf16_TFLOPs": PEAK_BF16_TFLOPS, "peak_HBM_TBps": PEAK_HBM_TBPS, "iters_per_window": a.iters,
+              "repeats": a.repeats, "shapes": {}}
+    for name, (s_img, s_txt, valid, H) in DENSE_SHAPES.items():
+        if a.dense_shapes and name not in a.dense_shapes:
+            continue
+        S = s_img + s_txt
+        torch.manual_seed(0)
+        q, k, v = [torch.randn(1, S, H, 128, device=dev, dtype=torch.bfloat16) for _ in range(3)]
+        cu = torch.tensor([0, s_img + valid, S], dtype=torch.int32, device=dev)
+        paths = {"old_lists": lambda: attention(q, k, v, cu_seqlens_q=cu, cu_seqlens_kv=cu),
+                 "new_varlen": lambda: attention(q, k, v, cu_seqlens_q=cu, cu_seqlens_kv=cu, kernel="varlen")}
+        outs = {n: f() for n, f in paths.items()}          # warm both (code objects, the cached lists)
+        torch.cuda.synchronize()
+        diff = (outs["old_lists"].float() - outs["new_varlen"].float()).abs().max().item()
+        del outs
+        ms = {n: [] for n in paths}
+        for _ in range(a.repeats):
+            for n, f in paths.items():                     # alternate the two inside every repeat
+                ms[n].append(timed(f, a.iters, warmup=0)[0])
+        n_valid, n_pad = s_img + valid, S - s_img - valid
+        flops = 4 * (n_valid ** 2 + n_pad ** 2) * 128 * H
+        t_flops = flops / (PEAK_BF16_TFLOPS * 1e12)
+        t_bytes = 4 * S * H * 128 * 2 / (PEAK_HBM_TBPS * 1e12)   # q, k, v read and o written once
+        row = {"S": S, "H": H, "segments": [n_valid, n_pad], "flop": flops, "max_abs_old_vs_new": diff,
+               "tolerance_bf16": 1e-2, "bound": "compute" if t_flops >= t_bytes else "memory"}
+        for n, xs in ms.items():
+            med = sorted(xs)[len(xs) // 2]
+            row[n] = {"ms_per_call": xs, "median_ms": med, "spread_ms": max(xs) - min(xs),
+                      "TFLOPs": flops / (med * 1e-3) / 1e12,
+                      "share_of_peak": max(t_flops, t_bytes) / (med * 1e-3)}
+        row["speedup_new_over_old"] = row["old_lists"]["median_ms"] / row["new_varlen"]["median_ms"]
+        record["shapes"][name] = row
+        print(json.dumps({name: row}), flush=True)
+        del q, k, v
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(record, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dense", action="store_true", help="A/B of the dense call: lists path vs the dense varlen kernel")
+    ap.add_argument("--dense-shapes", nargs="*", default=[], help="--dense: subset of " + ", ".join(DENSE_SHAPES))
+    ap.add_argument("--repeats", type=int, default=3, help="--dense: timed windows per path")
+    ap.add_argument("--out", default="profiles/dense_varlen_ab.json", help="--dense: where the record goes")
     ap.add_argument("--heads", type=int, default=24)
     ap.add_argument("--grid", type=int, nargs=3, default=[32, 45, 80])
     ap.add_argument("--drop", type=float, default=0.75)
@@ -60,6 +118,8 @@ def main():
                     help=">= 0: synthetic lists -- every odd query block shares this fraction of its list with the even "
                          "block in front of it (what Hilbert-adjacent blocks of a trained model look like); same counts")
     a = ap.parse_args()
+    if a.dense:
+        return dense_ab(a)
     dev = torch.device("cuda:0")
     t, h, w = a.grid
     S_img, tb = t * h * w, 2
