@@ -371,6 +371,37 @@ int jenga_dense_varlen_fwd(void* stream, const void* q, const void* k, const voi
                            int64_t v_sh, int64_t o_ss, int64_t o_sh, float sm_scale, int dtype);
 
 /* ---------------------------------------------------------------------------------------------------
+ * FP8 Q.K block-sparse attention (csrc/qattn.hip; additive exports inside ABI 4).  An opt-in variant of jenga_bsattn_fwd
+ * (same reference lines, attention_block_triton_diffres.py:38-136 and :371-380) whose QK^T runs on e4m3fn operands with
+ * v_mfma_f32_32x32x64_f8f6f4: half the K bytes through HBM, L2 and LDS, a quarter of the QK^T instructions.  P.V stays 16-bit.
+ *
+ * jenga_quant_fp8_blocks: x [B, n_blocks*128, H, 128] (dtype, strides in elements, multiples of 8) ->
+ *   x8 uint8 [B, n_blocks*128, H, 128] contiguous (OCP e4m3fn bytes), scale fp32 [B, H, n_blocks].  offset: fp32 [B, H, 128] or
+ *   NULL.  Per (b, h, 128-token block), in IEEE fp32:
+ *       xf = float(x) - offset[b,h,:]   (skipped when NULL);   amax = max |xf| over the block's 128 x 128 values;
+ *       s = fmaxf(amax, 1e-30f) / 448.0f;   x8 = e4m3fn_rne(xf / s)  (a true division);   scale[b,h,block] = s.
+ *   The offset is for K: one vector subtracted from every key adds q.offset to all logits of a query row, which softmax
+ *   ignores (SageAttention's K smoothing), while it takes a per-channel bias out of the 8-bit range.
+ * jenga_bsattn_fp8_fwd: the arguments of jenga_bsattn_fwd with q8 / k8 (uint8 [B,S,H,128], strides in elements, multiples of
+ *   16) and q_scale / k_scale (fp32 [B,H,n_blocks]) in place of q / k; vt is the unchanged jenga_pack_v workspace and o the
+ *   output, both in dtype; no `order`; flags: 0 or JENGA_ATTN_XCD_REMAP.  q and k below are the dequantised values
+ *   x8 * scale; there is no pre-scaled, re-rounded q.
+ *   image query blocks m < nq_img, for each kept kv block j of idx / cnt (ascending):
+ *       s = (q8.k8^T in fp32) * (q_scale[b,h,m] * k_scale[b,h,j] * sm_scale * log2 e) [+ text_amp if j >= text_block_start];
+ *       kv columns >= seqlens[b] are -inf, a kept block wholly behind seqlens[b] contributes nothing; base-2 online softmax
+ *       in fp32; P rounded to dtype before P.V; the row sum taken from the unrounded p; o = acc / l, one rounding.
+ *       Rows >= seqlens[b] (and rows without a single valid kept key) are written as zeros.
+ *   text query blocks m >= nq_img: every kv block, no length mask, no text_amp.
+ *   Deterministic.  Close to, not bit-equal with, jenga_bsattn_fwd (8-bit q and k). */
+int jenga_quant_fp8_blocks(void* stream, const void* x, void* x8, float* scale, const float* offset, int64_t B, int64_t H,
+                           int64_t n_blocks, int64_t x_sb, int64_t x_ss, int64_t x_sh, int dtype);
+int jenga_bsattn_fp8_fwd(void* stream, const void* q8, const float* q_scale, const void* k8, const float* k_scale,
+                         const void* vt, void* o, const int32_t* seqlens, const int32_t* idx, const int32_t* cnt, int64_t B,
+                         int64_t H, int64_t n_blocks, int64_t nq_img, int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t k_sb,
+                         int64_t k_ss, int64_t k_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh, float sm_scale,
+                         float text_amp, int64_t text_block_start, int dtype, int flags);
+
+/* ---------------------------------------------------------------------------------------------------
  * Ulysses head pack/unpack: the local halves of xFuserLongContextAttention.forward's SeqAllToAll4D calls
  * (hyvideo/modules/xdit_ring_atten.py:118-131 scatter heads / gather sequence, :212-217 the reverse).
  * The exchange itself is one RCCL all_to_all_single issued from the host (torch.distributed); these

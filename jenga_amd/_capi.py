@@ -61,6 +61,8 @@ SIGNATURES = {
     "jenga_stream_delay": (_i32, [_vp, ctypes.c_double]),
     "jenga_cross_attn_fwd": (_i32, [_vp] * 5 + [_i64] * 14 + [_f32, _i32]),
     "jenga_dense_varlen_fwd": (_i32, [_vp] * 7 + [_i64] * 12 + [_f32, _i32]),
+    "jenga_quant_fp8_blocks": (_i32, [_vp] * 5 + [_i64] * 6 + [_i32]),
+    "jenga_bsattn_fp8_fwd": (_i32, [_vp] * 10 + [_i64] * 13 + [_f32, _f32, _i64, _i32, _i32]),
     "jenga_linear_export_choices": (_i64, [_vp, _i64]),
     "jenga_linear_import_choices": (_i32, [_vp, _i64]),
     "jenga_linear_import_mismatches": (_i64, []),
@@ -770,6 +772,78 @@ def bsattn_fwd(q, k, vt, seqlens, idx, cnt, nq_img, sm_scale, text_amp, text_blo
             prof.launches += 1
             pairs = B * H * (n_blocks - nq_img) * n_blocks
             tot = (cnt.sum(dtype=torch.int64) if cnt is not None else 0) + pairs
+            prof.pairs = tot if prof.pairs is None else prof.pairs + tot
+            prof.per_launch.append((prof.tag, tot))
+            if idx is not None and nq_img > 1:
+                prof.last_lists = (idx, cnt)
+    return out
+
+
+def quant_fp8_blocks(x, offset=None):
+    """x [B,S,H,128] (bf16 / fp16, unit head_dim stride, S a multiple of 128) -> (x8 uint8 [B,S,H,128] of e4m3fn bytes, scale
+    fp32 [B,H,S/128]): per (b, h, 128-token block) s = max(amax |x - offset|, 1e-30) / 448, x8 = e4m3fn((x - offset) / s)
+    (csrc/qattn.hip).  offset: fp32 [B,H,128] or None (the K smoothing of block_sparse_attention(qk_dtype="fp8"))."""
+    _need_gpu(x, "quant_fp8_blocks")
+    if x.dim() != 4 or x.shape[3] != 128 or x.shape[1] % 128 or x.shape[1] == 0:
+        raise ValueError("quant_fp8_blocks: x must be [B, n*128, H, 128]")
+    B, S, H, _ = x.shape
+    if offset is not None and (tuple(offset.shape) != (B, H, 128) or offset.dtype != torch.float32
+                               or not offset.is_contiguous() or offset.device != x.device):
+        raise ValueError("quant_fp8_blocks: offset must be a contiguous float32 [B,H,128] tensor on x's device")
+    x8 = torch.empty((B, S, H, 128), dtype=torch.uint8, device=x.device)
+    scale = torch.empty((B, H, S // 128), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        _check(lib().jenga_quant_fp8_blocks(_stream(x.device), _p(x), _p(x8), _p(scale), _p(offset), B, H, S // 128,
+                                            *_bshd_strides(x), dtype_code(x.dtype)), "jenga_quant_fp8_blocks")
+    return x8, scale
+
+
+def bsattn_fp8_fwd(q8, q_scale, k8, k_scale, vt, seqlens, idx, cnt, nq_img, sm_scale, text_amp, text_block_start, out=None,
+                   xcd_remap=True):
+    """bsattn_fwd with e4m3fn q and k: q8, k8 uint8 [B,S,H,128] and q_scale, k_scale fp32 [B,H,S/128] from quant_fp8_blocks; vt
+    from pack_v (its dtype is the output's); seqlens / idx / cnt as for bsattn_fwd -> o [B,S,H,128] (csrc/qattn.hip)."""
+    _need_gpu(q8, "bsattn_fp8_fwd")
+    if q8.dim() != 4 or q8.shape[3] != 128 or q8.shape[1] % 128 or q8.dtype != torch.uint8 or k8.dtype != torch.uint8 \
+            or k8.shape != q8.shape:
+        raise ValueError("bsattn_fp8_fwd: q8 and k8 must be uint8 [B, n*128, H, 128] of one shape")
+    B, S, H, _ = q8.shape
+    n_blocks = S // 128
+    for name, t in (("q_scale", q_scale), ("k_scale", k_scale)):
+        if tuple(t.shape) != (B, H, n_blocks) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != q8.device:
+            raise ValueError(f"bsattn_fp8_fwd: {name} must be a contiguous float32 [B,H,n_blocks] tensor on q8's device")
+    if tuple(vt.shape) != (B, H, 2 * n_blocks, 128, 64) or not vt.is_contiguous() or vt.device != q8.device:
+        raise ValueError(f"bsattn_fp8_fwd: vt must be the contiguous pack_v workspace {(B, H, 2 * n_blocks, 128, 64)}")
+    dt = dtype_code(vt.dtype)
+    if out is None:
+        out = torch.empty((B, S, H, 128), dtype=vt.dtype, device=q8.device)
+    elif out.shape != q8.shape or out.dtype != vt.dtype or out.device != q8.device:
+        raise ValueError("bsattn_fp8_fwd: out must be [B,S,H,128] in vt's dtype")
+    if seqlens is not None and (seqlens.dtype != torch.int32 or seqlens.device != q8.device):
+        seqlens = seqlens.to(device=q8.device, dtype=torch.int32)
+    if seqlens is not None and seqlens.numel() < B:
+        raise ValueError(f"bsattn_fp8_fwd: seqlens has {seqlens.numel()} entries for batch {B}")
+    if not 0 <= nq_img <= n_blocks:
+        raise ValueError("bsattn_fp8_fwd: nq_img must lie in [0, n_blocks]")
+    if nq_img > 0 and (idx is None or cnt is None or tuple(idx.shape) != (B, H, nq_img, n_blocks)
+                       or tuple(cnt.shape) != (B, H, nq_img) or idx.dtype != torch.int32 or cnt.dtype != torch.int32
+                       or not idx.is_contiguous() or not cnt.is_contiguous() or idx.device != q8.device
+                       or cnt.device != q8.device):
+        raise ValueError("bsattn_fp8_fwd: idx / cnt must be contiguous int32 [B,H,nq_img,n_blocks] / [B,H,nq_img]")
+    prof = ATTN_PROFILE
+    with _on(q8.device):
+        if prof is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        _check(lib().jenga_bsattn_fp8_fwd(_stream(q8.device), _p(q8), _p(q_scale), _p(k8), _p(k_scale), _p(vt), _p(out),
+                                          _p(seqlens), _p(idx), _p(cnt), B, H, n_blocks, nq_img, *_bshd_strides(q8),
+                                          *_bshd_strides(k8), *_bshd_strides(out), float(sm_scale), float(text_amp),
+                                          int(text_block_start), dt, ATTN_XCD_REMAP if xcd_remap else 0),
+               "jenga_bsattn_fp8_fwd")
+        if prof is not None:
+            e1.record()
+            prof.events.append((e0, e1))
+            prof.launches += 1
+            tot = (cnt.sum(dtype=torch.int64) if cnt is not None else 0) + B * H * (n_blocks - nq_img) * n_blocks
             prof.pairs = tot if prof.pairs is None else prof.pairs + tot
             prof.per_launch.append((prof.tag, tot))
             if idx is not None and nq_img > 1:

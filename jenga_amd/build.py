@@ -42,6 +42,8 @@ SOURCES = [
     ("bsattn5.hip", ["-fno-honor-nans", "-fno-slp-vectorize", "-Wno-inline-asm"]),
     # the dense varlen kernel: the attention flags, and no packed fp32 by construction (NO_PK includes -fno-slp-vectorize)
     ("dattn.hip", ["-fno-honor-nans", "-Wno-inline-asm"] + NO_PK),
+    # the FP8 Q.K kernel and its quantiser: same flags (the quantiser's divisions are __fdiv_rn, its only arithmetic besides)
+    ("qattn.hip", ["-fno-honor-nans", "-Wno-inline-asm"] + NO_PK),
 ]
 
 def _hipcc():

@@ -8,6 +8,7 @@ Mirrors (same names, argument order, defaults, return layout):
 Everything numeric runs in libjenga_amd.so (HIP, gfx950) through jenga_amd._capi:
   jenga_block_pool + jenga_block_select  (reference :198-295)   selection -> ascending kept-block lists
   jenga_pack_v + jenga_bsattn_fwd        (reference :38-196, :371-380)   image rows + text rows in one launch
+  qk_dtype="fp8" (opt-in, jenga_amd extension): jenga_quant_fp8_blocks on q and k + jenga_bsattn_fp8_fwd in its place
 torch is used for allocation, views and zero-padding only.  No CPU fallback.
 """
 
@@ -42,28 +43,50 @@ def build_block_index(query, key, top_k, text_blocks, prob_threshold, block_neig
                               first_frame_blocks=first_frame_blocks, want_mask=want_mask, head_dim=head_dim)
 
 
+def _check_qk_dtype(qk_dtype, head_dim):
+    if qk_dtype not in (None, "fp8"):
+        raise ValueError(f"jenga_amd: qk_dtype must be None or 'fp8' (got {qk_dtype!r})")
+    if qk_dtype == "fp8" and head_dim != 128:
+        raise ValueError(f"jenga_amd: qk_dtype='fp8' needs head_dim 128 (got {head_dim})")
+
+
+def _attend_fp8(q, k, vt, kpool, seqlens, idx, cnt, nimg, text_amp, out=None):
+    """The FP8 Q.K path behind the (unchanged) selection: q and k quantised per 128-token block, K after subtracting its
+    mean over the sequence -- the mean of the block means the selection already has, so no further pass over K."""
+    q8, q_scale = _capi.quant_fp8_blocks(q)
+    k8, k_scale = _capi.quant_fp8_blocks(k, kpool.float().mean(2))
+    return _capi.bsattn_fp8_fwd(q8, q_scale, k8, k_scale, vt, seqlens, idx, cnt, nimg, 128 ** -0.5, text_amp, nimg, out=out)
+
+
 def attencarve_packed(q, k, vt, top_k, seqlens, text_blocks, text_amp, prob_threshold, block_neighbor_list,
-                      first_frame_blocks=0, out=None, return_lists=False, pooled=None):
+                      first_frame_blocks=0, out=None, return_lists=False, pooled=None, qk_dtype=None):
     """Core used by the DiT blocks: q/k [B,S,H,128] already normed+roped (any strides), vt = packed V workspace
     (jenga_pack_v), seqlens int32 [B] on the device.  Selection + one attention launch; returns o [B,S,H,128]
     (written into `out` if given, which may be a strided view, e.g. the left part of the single-stream blocks'
     concat buffer)."""
     B, S, H, D = q.shape
+    _check_qk_dtype(qk_dtype, D)
     nb = S // BLOCK
     nimg = nb - text_blocks
+    if qk_dtype == "fp8" and pooled is None:
+        pooled = (_capi.block_pool(q, nimg) if nimg > 0 else None, _capi.block_pool(k, nb))
     idx = cnt = None
     if nimg > 0:
         _, idx, cnt = build_block_index(q, k, top_k, text_blocks, prob_threshold, block_neighbor_list,
                                         first_frame_blocks, pooled=pooled)
-    o = _capi.bsattn_fwd(q, k, vt, seqlens, idx, cnt, nimg, D ** -0.5, text_amp, nimg, out=out)
+    if qk_dtype == "fp8":
+        o = _attend_fp8(q, k, vt, pooled[1], seqlens, idx, cnt, nimg, text_amp, out=out)
+    else:
+        o = _capi.bsattn_fwd(q, k, vt, seqlens, idx, cnt, nimg, D ** -0.5, text_amp, nimg, out=out)
     return (o, idx, cnt) if return_lists else o
 
 
 def _combined(query, key, value, top_k, seqlens, text_blocks, text_amp, prob_threshold, block_neighbor_list,
-              shape_xfuse, first_frame_blocks=0, context_size=None, return_mask=False):
+              shape_xfuse, first_frame_blocks=0, context_size=None, return_mask=False, qk_dtype=None):
     B, S, H, D = query.shape
     if D not in (16, 32, 64, 128):         # the Triton kernel's own assert (:155)
         raise ValueError(f"jenga_amd: head_dim must be 16, 32, 64 or 128 (got {D})")
+    _check_qk_dtype(qk_dtype, D)
     head_dim = D
     if D != 128:
         # Narrow heads run on the 128-channel kernels with zero channels appended: the extra products are exact zeros in
@@ -79,11 +102,17 @@ def _combined(query, key, value, top_k, seqlens, text_blocks, text_amp, prob_thr
     if nimg < 0:
         raise ValueError("text_blocks exceeds the number of blocks")
     mask = idx = cnt = None
+    pooled = None
+    if qk_dtype == "fp8":
+        pooled = (_capi.block_pool(query, nimg) if nimg > 0 else None, _capi.block_pool(key, nb))
     if nimg > 0:
         mask, idx, cnt = build_block_index(query, key, top_k, text_blocks, prob_threshold, block_neighbor_list,
-                                           first_frame_blocks, want_mask=return_mask, head_dim=head_dim)
+                                           first_frame_blocks, want_mask=return_mask, pooled=pooled, head_dim=head_dim)
     vt = _capi.pack_v(value, nb)
-    out = _capi.bsattn_fwd(query, key, vt, seqlens, idx, cnt, nimg, head_dim ** -0.5, text_amp, nimg)
+    if qk_dtype == "fp8":
+        out = _attend_fp8(query, key, vt, pooled[1], seqlens, idx, cnt, nimg, text_amp)
+    else:
+        out = _capi.bsattn_fwd(query, key, vt, seqlens, idx, cnt, nimg, head_dim ** -0.5, text_amp, nimg)
     if context_size is not None and context_size != S:
         out = out[:, :context_size]
     if head_dim != 128:
@@ -124,9 +153,12 @@ def block_sparse_attention(
     shape_xfuse: bool = False,
     p_remain_rates: float = 0.5,
     return_mask: bool = False,
+    qk_dtype: str = None,
 ):
     """HunyuanVideo flavour.  q/k/v [B,S,H,128], S % 128 == 0 (the reference's padding branch is dead code, :331-336),
-    cu_seqlens_q from get_cu_seqlens (only element [1] is used).  Returns [B,S,H*D], or [B,S,H,D] if shape_xfuse."""
+    cu_seqlens_q from get_cu_seqlens (only element [1] is used).  Returns [B,S,H*D], or [B,S,H,D] if shape_xfuse.
+    qk_dtype (jenga_amd extension, also on the I2V and Wan flavours): None = 16-bit Q.K (the default); "fp8" = the same kept
+    lists, then Q and K quantised per 128-token block to e4m3fn and QK^T on the FP8 MFMA (csrc/qattn.hip), head_dim 128 only."""
     _check_inputs(query, key, value)
     if block_size_M != BLOCK or block_size_N != BLOCK:
         raise ValueError("jenga_amd: block sizes must be 128")
@@ -137,7 +169,7 @@ def block_sparse_attention(
     query, key, value = _unit_inner(query), _unit_inner(key), _unit_inner(value)
     seqlens = _seqlens_from_cu(cu_seqlens_q, query.device)
     return _combined(query, key, value, top_k, seqlens, text_blocks, text_amp, p_remain_rates, block_neighbor_list,
-                     shape_xfuse, return_mask=return_mask)
+                     shape_xfuse, return_mask=return_mask, qk_dtype=qk_dtype)
 
 
 def _pad_seq(t, pad):
@@ -147,7 +179,7 @@ def _pad_seq(t, pad):
 def block_sparse_attention_i2v(query, key, value, top_k, block_size_M=128, block_size_N=128, cu_seqlens_q=None,
                                cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None, text_blocks=4,
                                text_amp=0.0, block_neighbor_list=None, shape_xfuse=False, p_remain_rates=0.5,
-                               return_mask=False):
+                               return_mask=False, qk_dtype=None):
     """HunyuanVideo-I2V flavour: pads S to a multiple of 128, text_blocks defaults to 4, output sliced back."""
     _check_inputs(query, key, value)
     if cu_seqlens_q is None:
@@ -157,13 +189,13 @@ def block_sparse_attention_i2v(query, key, value, top_k, block_size_M=128, block
     q, k, v = (_pad_seq(_unit_inner(t), pad) for t in (query, key, value))
     seqlens = _seqlens_from_cu(cu_seqlens_q, query.device)
     return _combined(q, k, v, top_k, seqlens, text_blocks, text_amp, p_remain_rates, block_neighbor_list,
-                     shape_xfuse, context_size=S, return_mask=return_mask)
+                     shape_xfuse, context_size=S, return_mask=return_mask, qk_dtype=qk_dtype)
 
 
 def block_sparse_attention_wan(query, key, value, top_k, block_size_M=128, block_size_N=128, cu_seqlens_q=None,
                                cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None, text_blocks=0,
                                text_amp=0.0, block_neighbor_list=None, shape_xfuse=False, p_remain_rates=0.9,
-                               first_frame_blocks=0, return_mask=False, kv_lens=None):
+                               first_frame_blocks=0, return_mask=False, kv_lens=None, qk_dtype=None):
     """Wan flavour: always pads, computes in bf16 whatever the input dtype, seqlen = unpadded S, dense first-frame
     rule, returns the input dtype.  kv_lens (int32 [B] tensor, jenga_amd extension): keys at or beyond it are masked
     -- what WanSelfAttention's dense branch gets from flash_attention(k_lens=seq_lens) (wan/modules/model_mul.py:153-159)
@@ -179,7 +211,8 @@ def block_sparse_attention_wan(query, key, value, top_k, block_size_M=128, block
     else:
         seqlens = torch.full((B,), S, dtype=torch.int32, device=query.device)
     res = _combined(q, k, v, top_k, seqlens, text_blocks, text_amp, p_remain_rates, block_neighbor_list,
-                    shape_xfuse, first_frame_blocks=first_frame_blocks, context_size=S, return_mask=return_mask)
+                    shape_xfuse, first_frame_blocks=first_frame_blocks, context_size=S, return_mask=return_mask,
+                    qk_dtype=qk_dtype)
     if return_mask:
         return res[0].to(out_dtype), res[1]
     return res.to(out_dtype)

@@ -80,11 +80,51 @@ def dense_ab(a):
         json.dump(record, f, indent=1)
 
 
+def fp8_ab(a, q, k, vt, seqlens, idx, cnt, nimg, kpool, flops, res):
+    """--fp8: the shipped 16-bit default against the FP8 Q.K kernel on the SAME tensors and kept lists, one process, alternating
+    windows of `--iters` calls (choose it so that a window is >= 1 s), `--repeats` windows each:
+      default    bsattn_fwd with ATTN_DEFAULT_FLAGS;
+      fp8_attn   bsattn_fp8_fwd alone (q8 / k8 quantised once, outside the windows);
+      fp8_total  the two quantiser launches (K with the mean-of-block-means offset) + bsattn_fp8_fwd."""
+    off = kpool.float().mean(2)
+    q8, qs = _capi.quant_fp8_blocks(q)
+    k8, ks = _capi.quant_fp8_blocks(k, off)
+    sm = 128 ** -0.5
+    attn8 = lambda a8, b8: _capi.bsattn_fp8_fwd(a8[0], a8[1], b8[0], b8[1], vt, seqlens, idx, cnt, nimg, sm, 0.0, nimg)
+    paths = {"default": lambda: _capi.bsattn_fwd(q, k, vt, seqlens, idx, cnt, nimg, sm, 0.0, nimg),
+             "fp8_attn": lambda: attn8((q8, qs), (k8, ks)),
+             "fp8_total": lambda: attn8(_capi.quant_fp8_blocks(q), _capi.quant_fp8_blocks(k, off))}
+    o16, o8 = paths["default"]().float(), paths["fp8_total"]().float()          # warm-up; the error figures
+    torch.cuda.synchronize()
+    d = o8 - o16
+    rec = {"shape": res["shape"], "pairs": res["pairs"], "flop": flops, "default_flags": _capi.ATTN_DEFAULT_FLAGS,
+           "iters_per_window": a.iters, "repeats": a.repeats, "finite": bool(torch.isfinite(o8).all().item()),
+           "fp8_vs_16bit_kernel": {"max_abs": float(d.abs().max().item()),
+                                   "rms_rel": float((d.pow(2).mean().sqrt() / o16.pow(2).mean().sqrt()).item())}}
+    del o16, o8, d
+    ms = {n: [] for n in paths}
+    for _ in range(a.repeats):
+        for n, f in paths.items():                     # alternate inside every repeat
+            ms[n].append(timed(f, a.iters, warmup=0)[0])
+    for n, xs in ms.items():
+        med = sorted(xs)[len(xs) // 2]
+        rec[n] = {"ms_per_call": xs, "median_ms": med, "spread_ms": max(xs) - min(xs),
+                  "TFLOPs": flops / (med * 1e-3) / 1e12}
+    rec["speedup_fp8_attn_over_default"] = rec["default"]["median_ms"] / rec["fp8_attn"]["median_ms"]
+    rec["speedup_fp8_total_over_default"] = rec["default"]["median_ms"] / rec["fp8_total"]["median_ms"]
+    print(json.dumps(rec), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.fp8_out)), exist_ok=True)
+    with open(a.fp8_out, "w") as f:
+        json.dump(rec, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fp8", action="store_true", help="A/B of the attention launch: 16-bit default vs the FP8 Q.K kernel")
+    ap.add_argument("--fp8-out", default="profiles/bsattn_fp8_ab.json", help="--fp8: where the record goes")
     ap.add_argument("--dense", action="store_true", help="A/B of the dense call: lists path vs the dense varlen kernel")
     ap.add_argument("--dense-shapes", nargs="*", default=[], help="--dense: subset of " + ", ".join(DENSE_SHAPES))
-    ap.add_argument("--repeats", type=int, default=3, help="--dense: timed windows per path")
+    ap.add_argument("--repeats", type=int, default=3, help="--dense / --fp8: timed windows per path")
     ap.add_argument("--out", default="profiles/dense_varlen_ab.json", help="--dense: where the record goes")
     ap.add_argument("--heads", type=int, default=24)
     ap.add_argument("--grid", type=int, nargs=3, default=[32, 45, 80])
@@ -210,6 +250,8 @@ def main():
     res["pairs"] = pairs
     res["kept_mean"] = kept / (H * nimg)
     res["kept_min_max"] = [int(cnt.min()), int(cnt.max())]
+    if a.fp8:
+        return fp8_ab(a, q, k, vt, seqlens, idx, cnt, nimg, kpool, flops, res)
     fl = a.flags
     if a.sorted:
         fl = (_capi.ATTN_DEFAULT_FLAGS if fl is None else fl) | _capi.ATTN_SORTED
