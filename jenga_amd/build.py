@@ -64,7 +64,7 @@ def _extra_flags():
 
 def source_digest():
     """sha256 over everything the library is built from: csrc/, the header, this file (the flags live here) AND the
-    effective JENGA_HIPCC_FLAGS -- an elimination build (-DLQ_X_NODMA=1 ...: wrong results by design) must never pass for
+    effective JENGA_HIPCC_FLAGS -- a library built with extra flags (an A/B build, tools/build_alt.py) must never pass for
     the product library on a later run."""
     import hashlib
     h = hashlib.sha256()

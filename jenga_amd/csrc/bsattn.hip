@@ -22,7 +22,7 @@
 // added to the logits of kv blocks >= text_block_start; kv columns >= seqlen are -inf; P is rounded to the
 // storage dtype before P.V; l accumulates the unrounded P; o = acc / l.  Text query blocks (TEXT=true) follow
 // flash_attn_func instead (:371-380): unrounded q, scores * sm_scale, no mask, no amp.
-#include "common.h"
+#include "attn_launch.h"
 
 namespace jenga {
 namespace {
@@ -35,14 +35,7 @@ struct AttnParams {
     const int32_t* seqlens;
     const int32_t* idx;
     const int32_t* cnt;
-    long long q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, o_sb, o_ss, o_sh;
-    int B, H, n_blocks, nq_img;
-    int text_block_start;
-    float qk_scale;   // sm_scale * log2(e), fp32
-    float text_amp;
-    int n_text_wg_pad;  // text workgroups (padded to a multiple of 8) come first in the grid
-    int img_per_head;   // grid slots per (b,h) for image blocks (8*C with XCD remap, nq_img otherwise)
-    int xcd_chunk;      // C, or 0 = plain order
+    AttnGeom g;
 };
 
 constexpr int KT = 64;                      // keys per LDS tile
@@ -122,16 +115,16 @@ __device__ __forceinline__ void attn_block(const AttnParams& P, unsigned char* s
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int lq = lane & 31, hi = lane >> 5;
-    const int seqlen = P.seqlens ? P.seqlens[b] : P.n_blocks * 128;
+    const int seqlen = P.seqlens ? P.seqlens[b] : P.g.n_blocks * 128;
 
     // ---- kept-block list ----
     const int32_t* list = nullptr;
     int nkept;
     if (TEXT) {
-        nkept = P.n_blocks;
+        nkept = P.g.n_blocks;
     } else {
-        const long long row = ((long long)b * P.H + h) * P.nq_img + m;
-        list = P.idx + row * P.n_blocks;
+        const long long row = ((long long)b * P.g.H + h) * P.g.nq_img + m;
+        list = P.idx + row * P.g.n_blocks;
         nkept = __builtin_amdgcn_readfirstlane(P.cnt[row]);
     }
 
@@ -139,7 +132,7 @@ __device__ __forceinline__ void attn_block(const AttnParams& P, unsigned char* s
     const long long qrow = (long long)m * 128 + wave * 32 + lq;
     uint4 qf[8];
     {
-        const uint16_t* qp = P.q + b * P.q_sb + qrow * P.q_ss + h * P.q_sh + hi * 8;
+        const uint16_t* qp = P.q + b * P.g.q_sb + qrow * P.g.q_ss + h * P.g.q_sh + hi * 8;
 #pragma unroll
         for (int ds = 0; ds < 8; ++ds) {
             uint4 raw = *reinterpret_cast<const uint4*>(qp + ds * 16);
@@ -147,7 +140,7 @@ __device__ __forceinline__ void attn_block(const AttnParams& P, unsigned char* s
                 float f[8];
                 unpack8<T>(raw, f);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) f[e] = f[e] * P.qk_scale;
+                for (int e = 0; e < 8; ++e) f[e] = f[e] * P.g.qk_scale;
                 raw = pack8<T>(f);
             }
             qf[ds] = raw;
@@ -166,10 +159,10 @@ __device__ __forceinline__ void attn_block(const AttnParams& P, unsigned char* s
     for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
     bool first = true;
     // output row pointer computed up front: lets the o_* strides die before the loop (SGPR pressure)
-    uint16_t* const op = P.o + b * P.o_sb + qrow * P.o_ss + h * P.o_sh + hi * 4;
+    uint16_t* const op = P.o + b * P.g.o_sb + qrow * P.g.o_ss + h * P.g.o_sh + hi * 4;
 
-    const uint16_t* kbh = P.k + b * P.k_sb + h * P.k_sh;
-    const uint16_t* vbh = P.vt + ((long long)b * P.H + h) * (long long)P.n_blocks * 2 * (128 * KT);
+    const uint16_t* kbh = P.k + b * P.g.k_sb + h * P.g.k_sh;
+    const uint16_t* vbh = P.vt + ((long long)b * P.g.H + h) * (long long)P.g.n_blocks * 2 * (128 * KT);
 
     // ---- loop-invariant LDS addresses (buffer / group / d-block offsets are compile-time immediates) ----
     int k_addr[8], v_addr[4];
@@ -183,7 +176,7 @@ __device__ __forceinline__ void attn_block(const AttnParams& P, unsigned char* s
     const unsigned smem_base =
         __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem);
     const int kr_ = 16 * wave_u + (lane >> 4), kc_ = lane & 15, ksw_ = lane >> 4;
-    const unsigned kss_b = (unsigned)P.k_ss * 2u;   // K row stride in bytes (64 rows x stride < 2^31, checked on the host)
+    const unsigned kss_b = (unsigned)P.g.k_ss * 2u;   // K row stride in bytes (64 rows x stride < 2^31, checked on the host)
     const unsigned k_src0 = (unsigned)(kr_ + 0) * kss_b + ((kc_ ^ (0 + ksw_)) << 4);
     const unsigned k_src1 = (unsigned)(kr_ + 4) * kss_b + ((kc_ ^ (4 + ksw_)) << 4);
     const unsigned k_src2 = (unsigned)(kr_ + 8) * kss_b + ((kc_ ^ (8 + ksw_)) << 4);
@@ -229,14 +222,14 @@ __device__ __forceinline__ void attn_block(const AttnParams& P, unsigned char* s
                 }                                                                                                \
                 if (TEXT) {                                                                                      \
                     _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                             \
-                        s0[r] = s0[r] * P.qk_scale + neg_m;                                                      \
-                        s1[r] = s1[r] * P.qk_scale + neg_m;                                                      \
+                        s0[r] = s0[r] * P.g.qk_scale + neg_m;                                                      \
+                        s1[r] = s1[r] * P.g.qk_scale + neg_m;                                                      \
                     }                                                                                            \
                 } else if (SLOW) {                                                                               \
-                    if (blk >= P.text_block_start) {                                                             \
+                    if (blk >= P.g.text_block_start) {                                                             \
                         _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                         \
-                            s0[r] += P.text_amp;                                                                 \
-                            s1[r] += P.text_amp;                                                                 \
+                            s0[r] += P.g.text_amp;                                                                 \
+                            s1[r] += P.g.text_amp;                                                                 \
                         }                                                                                        \
                     }                                                                                            \
                     if (key0 + KT > seqlen) {                                                                    \
@@ -344,7 +337,7 @@ __device__ __forceinline__ void attn_block(const AttnParams& P, unsigned char* s
     if (!TEXT) {
         while (n_fast > 0) {
             const int bl = __builtin_amdgcn_readfirstlane(list[n_fast - 1]);
-            if (bl >= P.text_block_start || (bl + 1) * 128 > seqlen) --n_fast; else break;
+            if (bl >= P.g.text_block_start || (bl + 1) * 128 > seqlen) --n_fast; else break;
         }
     }
     // The kept list is read 64 entries at a time into one VGPR (lane j holds entry base+j) and entries are pulled out
@@ -370,8 +363,8 @@ __device__ __forceinline__ void attn_block(const AttnParams& P, unsigned char* s
     if (nkept > 0) {
         LIST_GET(0, blk);
         // prologue: V(0) + K(0), then (dummy V into the free slot) + K(1); keep K(1) in flight
-        STAGE_TILE(kbh + (long long)blk * 128 * P.k_ss, vbh + (long long)blk * 2 * (128 * KT), 0, 0);
-        STAGE_TILE(kbh + ((long long)blk * 128 + KT) * P.k_ss, vbh + ((long long)blk * 2 + 1) * (128 * KT), 1, 1);
+        STAGE_TILE(kbh + (long long)blk * 128 * P.g.k_ss, vbh + (long long)blk * 2 * (128 * KT), 0, 0);
+        STAGE_TILE(kbh + ((long long)blk * 128 + KT) * P.g.k_ss, vbh + ((long long)blk * 2 + 1) * (128 * KT), 1, 1);
     }
     STAGE_WAIT_KEEP_K();
     __syncthreads();
@@ -381,14 +374,14 @@ __device__ __forceinline__ void attn_block(const AttnParams& P, unsigned char* s
         int nblk = blk;                                                                                          \
         if (i + 1 < nkept) LIST_GET(i + 1, nblk);                                                                \
         /* tile 2i: V(2i+1) = block i half 1 -> V slot 1; K(2i+2) = next block half 0 -> K slot (t+2)%3 */       \
-        STAGE_TILE(kbh + ((long long)nblk * 128) * P.k_ss, vbh + ((long long)blk * 2 + 1) * (128 * KT), ks_p2, 1); \
+        STAGE_TILE(kbh + ((long long)nblk * 128) * P.g.k_ss, vbh + ((long long)blk * 2 + 1) * (128 * KT), ks_p2, 1); \
         COMPUTE_TILE(ks_cur, 0, 0, SLOW);                                                                        \
         STAGE_WAIT_KEEP_K();                                                                                     \
         __syncthreads();                                                                                         \
         ks_cur = (ks_cur == 2) ? 0 : ks_cur + 1;                                                                 \
         ks_p2 = (ks_p2 == 2) ? 0 : ks_p2 + 1;                                                                    \
         /* tile 2i+1: V(2i+2) = next block half 0 -> V slot 0; K(2i+3) = next block half 1 */                    \
-        STAGE_TILE(kbh + ((long long)nblk * 128 + KT) * P.k_ss, vbh + ((long long)nblk * 2) * (128 * KT), ks_p2, 0); \
+        STAGE_TILE(kbh + ((long long)nblk * 128 + KT) * P.g.k_ss, vbh + ((long long)nblk * 2) * (128 * KT), ks_p2, 0); \
         COMPUTE_TILE(ks_cur, 1, 1, SLOW);                                                                        \
         STAGE_WAIT_KEEP_K();                                                                                     \
         __syncthreads();                                                                                         \
@@ -425,26 +418,26 @@ __device__ __forceinline__ void attn_block(const AttnParams& P, unsigned char* s
 template <typename T>
 __global__ void __launch_bounds__(256, 2) bsattn_fwd_kernel(AttnParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int n_text = P.n_blocks - P.nq_img;
+    const int n_text = P.g.n_blocks - P.g.nq_img;
     const int id = blockIdx.x;
-    if (id < P.n_text_wg_pad) {  // text query blocks first: longest work items start earliest
-        if (id >= P.B * P.H * n_text) return;
-        const int m = P.nq_img + id % n_text;
+    if (id < P.g.n_text_wg_pad) {  // text query blocks first: longest work items start earliest
+        if (id >= P.g.B * P.g.H * n_text) return;
+        const int m = P.g.nq_img + id % n_text;
         const int bh = id / n_text;
-        attn_block<T, true>(P, smem, bh / P.H, bh % P.H, m);
+        attn_block<T, true>(P, smem, bh / P.g.H, bh % P.g.H, m);
         return;
     }
-    const int li = id - P.n_text_wg_pad;
-    const int bh = li / P.img_per_head;
-    const int r = li % P.img_per_head;
+    const int li = id - P.g.n_text_wg_pad;
+    const int bh = li / P.g.img_per_head;
+    const int r = li % P.g.img_per_head;
     int m;
-    if (P.xcd_chunk) {  // workgroup id -> XCD is id % 8: give each XCD a contiguous range of query blocks
-        m = (r & 7) * P.xcd_chunk + (r >> 3);
-        if ((r >> 3) >= P.xcd_chunk || m >= P.nq_img) return;
+    if (P.g.xcd_chunk) {  // workgroup id -> XCD is id % 8: give each XCD a contiguous range of query blocks
+        m = (r & 7) * P.g.xcd_chunk + (r >> 3);
+        if ((r >> 3) >= P.g.xcd_chunk || m >= P.g.nq_img) return;
     } else {
         m = r;
     }
-    attn_block<T, false>(P, smem, bh / P.H, bh % P.H, m);
+    attn_block<T, false>(P, smem, bh / P.g.H, bh % P.g.H, m);
 }
 
 }  // namespace
@@ -458,37 +451,12 @@ extern "C" int jenga_bsattn_fwd(void* stream, const void* q, const void* k, cons
                                 int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t o_sb, int64_t o_ss,
                                 int64_t o_sh, float sm_scale, float text_amp, int64_t text_block_start, int dtype,
                                 int flags) {
-    if (!q || !k || !vt || !o || B <= 0 || H <= 0 || n_blocks <= 0 || nq_img < 0 || nq_img > n_blocks) {
-        set_error("jenga_bsattn_fwd: bad arguments");
-        return JENGA_EINVAL;
-    }
-    if (nq_img > 0 && (!idx || !cnt)) {
-        set_error("jenga_bsattn_fwd: idx/cnt are required when nq_img > 0");
-        return JENGA_EINVAL;
-    }
-    const int64_t strides[9] = {q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, o_sb, o_ss, o_sh};
-    for (int i = 0; i < 9; ++i)
-        if (strides[i] & 7) {
-            set_error("jenga_bsattn_fwd: strides must be multiples of 8 elements (16-byte rows)");
-            return JENGA_EINVAL;
-        }
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)vt & 15) || ((uintptr_t)o & 15)) {
-        set_error("jenga_bsattn_fwd: pointers must be 16-byte aligned");
-        return JENGA_EINVAL;
-    }
-    if (dtype != JENGA_BF16 && dtype != JENGA_FP16) {
-        set_error("jenga_bsattn_fwd: dtype must be bf16 or fp16");
-        return JENGA_EUNSUPPORTED;
-    }
-    if (k_ss <= 0 || k_ss > (1 << 23)) {  // per-lane 32-bit byte offsets inside a 64-row K tile
-        set_error("jenga_bsattn_fwd: key sequence stride %lld out of range", (long long)k_ss);
-        return JENGA_EINVAL;
-    }
-    if (flags & JENGA_ATTN_LP)
-        return jenga_bsattn_lp_launch(stream, q, k, vt, o, seqlens, idx, cnt, order, B, H, n_blocks, nq_img, q_sb, q_ss,
-                                      q_sh, k_sb, k_ss, k_sh, o_sb, o_ss, o_sh, sm_scale, text_amp, text_block_start,
-                                      dtype, flags);
-    (void)order;   // a scheduling hint: the round-1 kernel below keeps its plain order
+    const AttnArgs a = {(hipStream_t)stream, q, k, vt, o, seqlens, idx, cnt, order, B, H, n_blocks, nq_img, q_sb, q_ss, q_sh,
+                        k_sb, k_ss, k_sh, o_sb, o_ss, o_sh, sm_scale, text_amp, text_block_start, dtype, flags};
+    // k_ss: per-lane 32-bit byte offsets inside a 64-row K tile
+    if (const int rc = attn_check_args("jenga_bsattn_fwd", a, "idx/cnt", 1, 1 << 23, "key sequence")) return rc;
+    if (flags & JENGA_ATTN_LP) return jenga_bsattn_lp_launch(a);
+    // (order is a scheduling hint: the round-1 kernel below keeps its plain order)
     AttnParams P;
     P.q = (const uint16_t*)q;
     P.k = (const uint16_t*)k;
@@ -497,42 +465,9 @@ extern "C" int jenga_bsattn_fwd(void* stream, const void* q, const void* k, cons
     P.seqlens = seqlens;
     P.idx = idx;
     P.cnt = cnt;
-    P.q_sb = q_sb; P.q_ss = q_ss; P.q_sh = q_sh;
-    P.k_sb = k_sb; P.k_ss = k_ss; P.k_sh = k_sh;
-    P.o_sb = o_sb; P.o_ss = o_ss; P.o_sh = o_sh;
-    P.B = (int)B; P.H = (int)H; P.n_blocks = (int)n_blocks; P.nq_img = (int)nq_img;
-    P.text_block_start = (int)text_block_start;
-    P.qk_scale = (float)((double)sm_scale * 1.44269504);
-    P.text_amp = text_amp;
-    const long long n_text = n_blocks - nq_img;
-    const long long n_text_wg = B * H * n_text;
-    P.n_text_wg_pad = (int)((n_text_wg + 7) / 8 * 8);
-    if ((flags & JENGA_ATTN_XCD_REMAP) && nq_img >= 64) {
-        P.xcd_chunk = (int)((nq_img + 7) / 8);
-        P.img_per_head = P.xcd_chunk * 8;
-    } else {
-        P.xcd_chunk = 0;
-        P.img_per_head = (int)nq_img;
-    }
-    const long long grid = (long long)P.n_text_wg_pad + B * H * (long long)P.img_per_head;
-    if (grid <= 0 || grid > 0x7fffffffLL) {
-        set_error("jenga_bsattn_fwd: grid size %lld out of range", grid);
-        return JENGA_EINVAL;
-    }
-    hipError_t e;
-    const size_t smem = W4_LDS_BYTES;
-    static bool smem_set[2][64] = {};
-    if (dtype == JENGA_BF16) {
-        lp_set_smem_once((const void*)bsattn_fwd_kernel<BF16>, (int)smem, smem_set[0]);
-        hipLaunchKernelGGL(bsattn_fwd_kernel<BF16>, dim3((unsigned)grid), dim3(256), smem, (hipStream_t)stream, P);
-    } else {
-        lp_set_smem_once((const void*)bsattn_fwd_kernel<FP16>, (int)smem, smem_set[1]);
-        hipLaunchKernelGGL(bsattn_fwd_kernel<FP16>, dim3((unsigned)grid), dim3(256), smem, (hipStream_t)stream, P);
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("jenga_bsattn_fwd: %s", hipGetErrorString(e));
-        return JENGA_ELAUNCH;
-    }
-    return JENGA_OK;
+    attn_fill_geom(P.g, a);
+    const long long grid = attn_plan_grid("jenga_bsattn_fwd", P.g, B * H, n_blocks - nq_img, nq_img, flags);
+    if (!grid) return JENGA_EINVAL;
+    return attn_launch_result("jenga_bsattn_fwd",
+                              ATTN_LAUNCH(dtype, bsattn_fwd_kernel, W4_LDS_BYTES, P, grid, a.stream));
 }

@@ -44,6 +44,7 @@
 // position modes) are measured, recorded in profiles/r04_attn_*.json and DESIGN.md, and gone from the source (git 882bacf).
 #include <cstdlib>
 
+#include "attn_launch.h"
 #include "lp_balance.h"
 #include "lp_core.h"
 
@@ -59,6 +60,7 @@ struct LpParams {
     const int32_t* idx;
     const int32_t* cnt;
     const int32_t* order;   // optional launch-order hint: position -> query block, per (b, h) (jenga_order_by_count)
+    // (the shared fields of AttnGeom, kept flat and in this order: embedding the struct moves this kernel's kernarg loads)
     long long q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, o_sb, o_ss, o_sh;
     int B, H, n_blocks, nq_img;
     int text_block_start;
@@ -375,103 +377,43 @@ __global__ void __launch_bounds__(LP_THREADS, 2) bsattn_lp_kernel(LpParams P) {
     attn_block_lp<T, false>(P, smem, bh / P.H, bh % P.H, m);
 }
 
-template <typename T, int VARIANT>
-static hipError_t lp_launch(const LpParams& P, long long grid, hipStream_t stream) {
-    static bool smem_set[64] = {};
-    lp_set_smem_once((const void*)bsattn_lp_kernel<T, VARIANT>, LP_LDS_BYTES, smem_set);
-    hipLaunchKernelGGL((bsattn_lp_kernel<T, VARIANT>), dim3((unsigned)grid), dim3(LP_THREADS), LP_LDS_BYTES, stream, P);
-    return hipGetLastError();
-}
-
 }  // namespace
 }  // namespace jenga
 
 using namespace jenga;
 
-// same arguments as jenga_bsattn_fwd (bsattn.hip); reached through it with JENGA_ATTN_LP
-int jenga_bsattn_lp_launch(void* stream, const void* q, const void* k, const void* vt, void* o, const int32_t* seqlens,
-                           const int32_t* idx, const int32_t* cnt, const int32_t* order, int64_t B, int64_t H,
-                           int64_t n_blocks, int64_t nq_img, int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t k_sb,
-                           int64_t k_ss, int64_t k_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh, float sm_scale,
-                           float text_amp, int64_t text_block_start, int dtype, int flags) {
+// the arguments of jenga_bsattn_fwd (bsattn.hip), validated there; reached through it with JENGA_ATTN_LP
+int jenga::jenga_bsattn_lp_launch(const AttnArgs& a) {
     LpParams P;
-    P.q = (const uint16_t*)q;
-    P.k = (const uint16_t*)k;
-    P.vt = (const uint16_t*)vt;
-    P.o = (uint16_t*)o;
-    P.seqlens = seqlens;
-    P.idx = idx;
-    P.cnt = cnt;
-    P.order = order;
-    P.q_sb = q_sb; P.q_ss = q_ss; P.q_sh = q_sh;
-    P.k_sb = k_sb; P.k_ss = k_ss; P.k_sh = k_sh;
-    P.o_sb = o_sb; P.o_ss = o_ss; P.o_sh = o_sh;
-    P.B = (int)B; P.H = (int)H; P.n_blocks = (int)n_blocks; P.nq_img = (int)nq_img;
-    P.text_block_start = (int)text_block_start;
-    P.qk_scale = (float)((double)sm_scale * 1.44269504);
-    P.text_amp = text_amp;
-    const long long n_text = n_blocks - nq_img;
-    const long long n_text_wg = B * H * n_text;
-    P.n_text_q = (int)n_text;
-    P.q_text0 = (int)nq_img;
+    P.q = (const uint16_t*)a.q;
+    P.k = (const uint16_t*)a.k;
+    P.vt = (const uint16_t*)a.vt;
+    P.o = (uint16_t*)a.o;
+    P.seqlens = a.seqlens;
+    P.idx = a.idx;
+    P.cnt = a.cnt;
+    P.order = a.order;
+    attn_fill_geom(P, a);
+    P.n_text_q = (int)(a.n_blocks - a.nq_img);
+    P.q_text0 = (int)a.nq_img;
     P.text_kv_len = 0;
     P.bal_set = 0;
-    P.n_text_wg_pad = (int)((n_text_wg + 7) / 8 * 8);
-    if ((flags & JENGA_ATTN_XCD_REMAP) && nq_img >= 64) {
-        P.xcd_chunk = (int)((nq_img + 7) / 8);
-        P.img_per_head = P.xcd_chunk * 8;
-    } else {
-        P.xcd_chunk = 0;
-        P.img_per_head = (int)nq_img;
-    }
-    if (k_ss < 0 || k_ss >= (1LL << 31)) {
-        set_error("jenga_bsattn_fwd: k token stride %lld out of range", (long long)k_ss);
+    if (a.k_ss < 0 || a.k_ss >= (1LL << 31)) {
+        set_error("jenga_bsattn_fwd: k token stride %lld out of range", (long long)a.k_ss);
         return JENGA_EINVAL;
     }
-    const long long grid = (long long)P.n_text_wg_pad + B * H * (long long)P.img_per_head;
-    if (grid <= 0 || grid > 0x7fffffffLL) {
-        set_error("jenga_bsattn_fwd: grid size %lld out of range", grid);
-        return JENGA_EINVAL;
-    }
-    // the balanced launch keeps per-device state that is ordered by events: that cannot be recorded into a HIP graph, so a
-    // capturing stream gets the plain static launch
-    if (flags & JENGA_ATTN_BALANCE) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) {
-            (void)hipGetLastError();      // (the query itself failed: not this launch's error)
-            cap = hipStreamCaptureStatusActive;
-        }
-        if (cap != hipStreamCaptureStatusNone) flags &= ~JENGA_ATTN_BALANCE;
-    }
-    // JENGA_ATTN_BALANCE: query blocks drawn from per-XCD queues, grid oversubscribed by 1/8 (JENGA_BALANCE_EXTRA_PCT, at
-    // least 8 workgroups) so that a fast XCD has workgroups left to draw from a slow one's queue
-    long long grid_bal = 0;
-    int bal_slot = -1;
-    if ((flags & JENGA_ATTN_BALANCE) && P.xcd_chunk && (P.n_text_wg_pad & 7) == 0 && (P.img_per_head & 7) == 0) {
-        const long long img = B * H * (long long)P.img_per_head;
-        long long extra = ((img * lp_balance_extra_pct() / 100) + 7) & ~7LL;
-        extra = extra < 8 ? 8 : extra;
-        if (grid + extra <= 0x7fffffffLL && B * H * (long long)P.xcd_chunk < (1LL << 28)) {
-            bal_slot = lp_balance_acquire((hipStream_t)stream);
-            if (bal_slot >= 0) {
-                grid_bal = grid + extra;
-                P.bal_set = bal_slot;
-            }
-        }
-    }
+    long long grid = attn_plan_grid("jenga_bsattn_fwd", P, a.B * a.H, a.n_blocks - a.nq_img, a.nq_img, a.flags);
+    if (!grid) return JENGA_EINVAL;
+    const int bal_slot = lp_balance_plan(a.stream, a.flags, P, a.B * a.H, &grid);
     hipError_t e;
-    if (grid_bal)
-        e = dtype == JENGA_BF16 ? lp_launch<BF16, 4>(P, grid_bal, (hipStream_t)stream)
-                                : lp_launch<FP16, 4>(P, grid_bal, (hipStream_t)stream);
-    else
-        e = dtype == JENGA_BF16 ? lp_launch<BF16, 0>(P, grid, (hipStream_t)stream)
-                                : lp_launch<FP16, 0>(P, grid, (hipStream_t)stream);
-    if (bal_slot >= 0) lp_balance_release(bal_slot, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        set_error("jenga_bsattn_fwd (lp): %s", hipGetErrorString(e));
-        return JENGA_ELAUNCH;
+    if (bal_slot >= 0) {
+        P.bal_set = bal_slot;
+        e = ATTN_LAUNCH_V(a.dtype, bsattn_lp_kernel, 4, LP_LDS_BYTES, P, grid, a.stream);
+        lp_balance_release(bal_slot, a.stream);
+    } else {
+        e = ATTN_LAUNCH_V(a.dtype, bsattn_lp_kernel, 0, LP_LDS_BYTES, P, grid, a.stream);
     }
-    return JENGA_OK;
+    return attn_launch_result("jenga_bsattn_fwd (lp)", e);
 }
 
 // Dense cross-attention on the same kernel: every query block runs in TEXT mode (all kv blocks, fp32 scores x
@@ -494,33 +436,23 @@ extern "C" int jenga_cross_attn_fwd(void* stream, const void* q, const void* k, 
         set_error("jenga_cross_attn_fwd: dtype must be bf16 or fp16");
         return JENGA_EUNSUPPORTED;
     }
+    const AttnArgs a = {(hipStream_t)stream, q, k, vt, o, nullptr, nullptr, nullptr, nullptr, B, H, nkv_blocks, 0, q_sb, q_ss, q_sh,
+                        k_sb, k_ss, k_sh, o_sb, o_ss, o_sh, sm_scale, 0.f, nkv_blocks, dtype, 0};
     LpParams P;
     P.q = (const uint16_t*)q; P.k = (const uint16_t*)k; P.vt = (const uint16_t*)vt; P.o = (uint16_t*)o;
     P.seqlens = nullptr; P.idx = nullptr; P.cnt = nullptr; P.order = nullptr;
-    P.q_sb = q_sb; P.q_ss = q_ss; P.q_sh = q_sh;
-    P.k_sb = k_sb; P.k_ss = k_ss; P.k_sh = k_sh;
-    P.o_sb = o_sb; P.o_ss = o_ss; P.o_sh = o_sh;
-    P.B = (int)B; P.H = (int)H; P.n_blocks = (int)nkv_blocks; P.nq_img = 0;
-    P.text_block_start = (int)nkv_blocks;
-    P.qk_scale = (float)((double)sm_scale * 1.44269504);
-    P.text_amp = 0.f;
+    attn_fill_geom(P, a);
     P.n_text_q = (int)nq_blocks;
     P.q_text0 = 0;
     P.text_kv_len = (kv_len == nkv_blocks * 128) ? 0 : (int)kv_len;     // 0: every tile whole, no mask needed
-    const long long wg = B * H * nq_blocks;
-    P.n_text_wg_pad = (int)((wg + 7) / 8 * 8);
-    P.xcd_chunk = 0;
-    P.img_per_head = 0;
     P.bal_set = 0;
+    const long long wg = B * H * nq_blocks;
     if (wg > 0x7ffffff0LL) {
         set_error("jenga_cross_attn_fwd: grid size %lld out of range", wg);
         return JENGA_EINVAL;
     }
-    const hipError_t e = dtype == JENGA_BF16 ? lp_launch<BF16, 2>(P, P.n_text_wg_pad, (hipStream_t)stream)
-                                             : lp_launch<FP16, 2>(P, P.n_text_wg_pad, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        set_error("jenga_cross_attn_fwd: %s", hipGetErrorString(e));
-        return JENGA_ELAUNCH;
-    }
-    return JENGA_OK;
+    const long long grid = attn_plan_grid("jenga_cross_attn_fwd", P, B * H, nq_blocks, 0, 0);   // text items only
+    if (!grid) return JENGA_EINVAL;
+    return attn_launch_result("jenga_cross_attn_fwd",
+                              ATTN_LAUNCH_V(dtype, bsattn_lp_kernel, 2, LP_LDS_BYTES, P, grid, a.stream));
 }

@@ -29,31 +29,9 @@
 #include <cstdlib>
 
 #define LP_QK_MFMA_ASM 1     // see lp_core.h: QK^T MFMAs with explicit register classes
+#include "attn_launch.h"
 #include "lp_balance.h"
 #include "lp_core.h"
-
-// elimination switches for A/B builds (tools/build_alt5.sh; results are WRONG with any of them, only the clock is read)
-#ifndef LQ_X_NODMA
-#define LQ_X_NODMA 0      // no LDS-DMA in the unrolled main loop
-#endif
-#ifndef LQ_X_NOBAR
-#define LQ_X_NOBAR 0      // no vmcnt wait / barrier at the end of a step of the unrolled main loop
-#endif
-#ifndef LQ_AHEAD
-#define LQ_AHEAD 4        // fragment reads run this many fragments (= twice as many MFMAs) ahead of their MFMAs
-#endif
-#ifndef LQ_DMA_SLOT0
-#define LQ_DMA_SLOT0 3    // the four LDS-DMA pieces of a block go out in slots LQ_DMA_SLOT0 + 8 i
-#endif
-#ifndef LQ_WAIT_PAIR
-#define LQ_WAIT_PAIR 0    // round 6: one counted lgkmcnt wait per FOUR MFMAs (two fragments) instead of one per two
-#endif
-#ifndef LQ_X_NOSM
-#define LQ_X_NOSM 0       // no softmax arithmetic in lq_bb (P = const, no exact-path ballot)
-#endif
-#ifndef LQ_X_NOREAD
-#define LQ_X_NOREAD 0     // no fragment reads in lq_bb (MFMAs on whatever the registers hold), no lgkmcnt waits
-#endif
 
 namespace jenga {
 namespace {
@@ -67,6 +45,7 @@ struct LqParams {
     const int32_t* pidx;   // [B,H,npair_img,n_blocks]: shared blocks, then A-only, then B-only (each ascending)
     const int32_t* pcnt;   // [B,H,npair_img,4]: n_shared, n_a, n_b, 0
     const int32_t* order;  // optional launch-order hint: position -> pair, per (b, h) (jenga_order_by_count on the pair work)
+    // (the shared fields of AttnGeom, kept flat and in this order: embedding the struct moves this kernel's kernarg loads)
     long long q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, o_sb, o_ss, o_sh;
     int B, H, n_blocks, nq_img;
     int npair_img, npair_txt;
@@ -94,28 +73,23 @@ __device__ __forceinline__ void lq_bb(LpState& sa, LpState& sb, const unsigned c
     constexpr int KO = KOFF < 0 ? 0 : KOFF, VO = VOFF < 0 ? 0 : VOFF;
     static_assert(PRE == 0 || (DO_QK && DO_PV), "the cross-block fragment pipeline is for full blocks");
     static_assert(PRE != 1 || HALF == 0, "only the first half prefetches (the next tile may still be in flight)");
-    constexpr int LAST = PRE == 1 ? 15 + LQ_AHEAD : (DO_PV ? 15 : 7);     // last fragment this block requests
+    constexpr int LAST = PRE == 1 ? 19 : (DO_PV ? 15 : 7);     // last fragment this block requests
     f32x16 zero16;
 #pragma unroll
     for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
     uint4 frv[8];
-    if (LQ_X_NOREAD) {
-#pragma unroll
-        for (int f = 0; f < 8; ++f) frv[f] = frk[f];
-    }
     float tt[32], xx[32];
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float halfA = 0.f, halfB = 0.f;
     uint32_t ww[16];
 #define LQ_READ(F_)                                                                                                   \
     do {                                                                                                              \
-        if (LQ_X_NOREAD) {                                                                                            \
-        } else if ((F_) < 8) {                                                                                               \
+        if ((F_) < 8) {                                                                                               \
             if (DO_QK) frk[(F_) & 7] = *reinterpret_cast<const uint4*>(kt + k_addr[(F_) & 7] + (HALF * 8192 + KO));   \
         } else if ((F_) < 16) {                                                                                       \
             if (DO_PV) frv[(F_) & 7] = *reinterpret_cast<const uint4*>(vt + v_addr[2 * HALF + (((F_) - 8) >> 2)] +    \
                                                                        ((((F_) - 8) & 3) * 4096 + VO));               \
-        } else if ((F_) < 16 + LQ_AHEAD && PRE == 1) { /* K fragment (F_ - 16) of the next block: the other half of this tile */ \
+        } else if ((F_) < 20 && PRE == 1) { /* K fragment (F_ - 16) of the next block: the other half of this tile */ \
             frk[(F_) & 7] = *reinterpret_cast<const uint4*>(kt + k_addr[(F_) & 7] + (8192 + KO));                     \
         }                                                                                                             \
     } while (0)
@@ -127,36 +101,31 @@ __device__ __forceinline__ void lq_bb(LpState& sa, LpState& sb, const unsigned c
 #define LQ_SM_X(E_) ((E_) < 4 ? ((E_) >> 1) : (E_) - 2)
 #define LQ_SM_ADD(E_)                                                                                                 \
     do {                                                                                                              \
-        if (!LP_ROWSUM_DOT2) {                                                                                        \
-            if (((E_) & 15) < 4) acc[((E_) >> 4) * 4 + ((E_) & 3)] = xx[E_];                                          \
-            else acc[((E_) >> 4) * 4 + ((E_) & 3)] += xx[E_];                                                         \
-        }                                                                                                             \
+        if (((E_) & 15) < 4) acc[((E_) >> 4) * 4 + ((E_) & 3)] = xx[E_];                                              \
+        else acc[((E_) >> 4) * 4 + ((E_) & 3)] += xx[E_];                                                             \
         if ((E_) & 1) {                                                                                               \
             ww[(E_) >> 1] = pack2<T>(xx[(E_) - 1], xx[E_]);                                                           \
-            /* LP_ROWSUM_DOT2: one chain per sub-block, c + lo + hi of the packed pair (lp_core.h); in front of the pin */ \
-            if (LP_ROWSUM_DOT2)                                                                                       \
-                acc[((E_) >> 4) * 4] = lp_pair_sum<T>(ww[(E_) >> 1], ((E_) & 15) == 1 ? 0.f : acc[((E_) >> 4) * 4]);  \
             asm volatile("" : "+v"(ww[(E_) >> 1]));   /* stay in this slot */                                         \
         }                                                                                                             \
     } while (0)
 #define LQ_SM(M_)                                                                                                     \
     do {                                                                                                              \
-        if (DO_SM && !LQ_X_NOSM) {                                                                                    \
+        if (DO_SM) {                                                                                                  \
             if (TEXT) {                                                                                               \
                 if ((M_) >= 2 && (M_) < 34) LQ_SM_ADD(((M_) - 2) & 31);                                               \
                 if ((M_) >= 1 && (M_) < 33) xx[((M_) - 1) & 31] = __builtin_amdgcn_exp2f(tt[((M_) - 1) & 31]);        \
                 if ((M_) < 32) tt[(M_) & 31] = LQ_SP((M_) & 31) * qk_scale + ((((M_) & 31) >> 4) ? sb.neg_m : sa.neg_m); \
                 if ((M_) == 33) {                                                                                     \
-                    halfA = LP_ROWSUM_DOT2 ? acc[0] : (acc[0] + acc[1]) + (acc[2] + acc[3]);                          \
-                    halfB = LP_ROWSUM_DOT2 ? acc[4] : (acc[4] + acc[5]) + (acc[6] + acc[7]);                          \
+                    halfA = (acc[0] + acc[1]) + (acc[2] + acc[3]);                                                    \
+                    halfB = (acc[4] + acc[5]) + (acc[6] + acc[7]);                                                    \
                 }                                                                                                     \
             } else {                                                                                                  \
                 _Pragma("unroll") for (int e_ = 0; e_ < 32; ++e_)                                                     \
                     if (LQ_SM_X(e_) + 1 == (M_)) LQ_SM_ADD(e_);                                                       \
                 _Pragma("unroll") for (int e_ = 0; e_ < 32; ++e_)                                                     \
                     if (LQ_SM_X(e_) == (M_)) xx[e_] = __builtin_amdgcn_exp2f(LQ_SP(e_));                              \
-                if ((M_) == 15) halfA = LP_ROWSUM_DOT2 ? acc[0] : (acc[0] + acc[1]) + (acc[2] + acc[3]);              \
-                if ((M_) == 31) halfB = LP_ROWSUM_DOT2 ? acc[4] : (acc[4] + acc[5]) + (acc[6] + acc[7]);              \
+                if ((M_) == 15) halfA = (acc[0] + acc[1]) + (acc[2] + acc[3]);                                        \
+                if ((M_) == 31) halfB = (acc[4] + acc[5]) + (acc[6] + acc[7]);                                        \
             }                                                                                                         \
         }                                                                                                             \
     } while (0)
@@ -165,27 +134,15 @@ __device__ __forceinline__ void lq_bb(LpState& sa, LpState& sb, const unsigned c
         if ((N_) == 1) __builtin_amdgcn_s_waitcnt(0xC17F);                                                            \
         else if ((N_) == 2) __builtin_amdgcn_s_waitcnt(0xC27F);                                                       \
         else if ((N_) == 3) __builtin_amdgcn_s_waitcnt(0xC37F);                                                       \
-        else if ((N_) == 4) __builtin_amdgcn_s_waitcnt(0xC47F);                                                       \
-        else if ((N_) == 5) __builtin_amdgcn_s_waitcnt(0xC57F);                                                       \
-        else if ((N_) == 6) __builtin_amdgcn_s_waitcnt(0xC67F);                                                       \
-        else if ((N_) == 7) __builtin_amdgcn_s_waitcnt(0xC77F);                                                       \
         else __builtin_amdgcn_s_waitcnt(0xC07F);                                                                      \
     } while (0)
     /* slot m, m even, issues the MFMAs m and m + 1 on fragment m >> 1: that fragment must be there; the reads requested
        behind it are fragments (m >> 1) + 1 .. min((m >> 1) + 3, LAST) */
 #define LQ_SLOT(M_)                                                                                                   \
     do {                                                                                                              \
-        if (!LQ_X_NOREAD && !((M_) & 1) && (((M_) < 16 && DO_QK) || ((M_) >= 16 && DO_PV))) {                         \
-            if (!LQ_WAIT_PAIR) {                                                                                      \
-                LQ_LGKM(LAST - ((M_) >> 1) < LQ_AHEAD - 1 ? LAST - ((M_) >> 1) : LQ_AHEAD - 1);                       \
-                __builtin_amdgcn_sched_barrier(0);   /* or hipcc moves the MFMA above the wait and adds its own */    \
-            } else if (((M_) & 3) == 0) {                                                                             \
-                /* one wait per FOUR MFMAs: fragments f = m >> 1 and f + 1 must both be there; requested behind */    \
-                /* them: f + 2 .. min(f + LQ_AHEAD - 1, LAST) */                                                      \
-                LQ_LGKM(LAST - ((M_) >> 1) - 1 < LQ_AHEAD - 2 ? (LAST - ((M_) >> 1) - 1 < 0 ? 0 : LAST - ((M_) >> 1) - 1) \
-                                                              : LQ_AHEAD - 2);                                        \
-                __builtin_amdgcn_sched_barrier(0);                                                                    \
-            }                                                                                                         \
+        if (!((M_) & 1) && (((M_) < 16 && DO_QK) || ((M_) >= 16 && DO_PV))) {                                         \
+            LQ_LGKM(LAST - ((M_) >> 1) < 3 ? LAST - ((M_) >> 1) : 3);                                                 \
+            __builtin_amdgcn_sched_barrier(0);   /* or hipcc moves the MFMA above the wait and adds its own */        \
         }                                                                                                             \
         if ((M_) < 16) {                                                                                              \
             if (DO_QK) {                                                                                              \
@@ -205,29 +162,23 @@ __device__ __forceinline__ void lq_bb(LpState& sa, LpState& sb, const unsigned c
                 sa.o[(((M_) - 16) >> 1) & 3] = mfma32<T>(frv[(((M_) - 16) >> 1) & 7], poA[((M_) - 16) >> 3],          \
                                                          sa.o[(((M_) - 16) >> 1) & 3]);                               \
         }                                                                                                             \
-        if (((M_) & 1) == 0 && !(!DO_QK && ((M_) >> 1) + LQ_AHEAD < 8 + LQ_AHEAD)) {                                  \
-            LQ_READ(((M_) >> 1) + LQ_AHEAD);                                                                          \
+        if (((M_) & 1) == 0 && (DO_QK || (M_) >= 16)) {   /* drain forms: fragments 8..11 read up front */            \
+            LQ_READ(((M_) >> 1) + 4);                                                                                 \
         }                                                                                                             \
-        if (dma && !LQ_X_NODMA) {                                                                                     \
-            if ((M_) == LQ_DMA_SLOT0) lp_stage1<0>(*dma);                                                             \
-            if ((M_) == LQ_DMA_SLOT0 + 8) lp_stage1<1>(*dma);                                                         \
-            if ((M_) == LQ_DMA_SLOT0 + 16) lp_stage1<2>(*dma);                                                        \
-            if ((M_) == LQ_DMA_SLOT0 + 24) lp_stage1<3>(*dma);                                                        \
+        if (dma) {   /* the four LDS-DMA pieces of a block go out in slots 3 + 8 i */                                 \
+            if ((M_) == 3) lp_stage1<0>(*dma);                                                                        \
+            if ((M_) == 11) lp_stage1<1>(*dma);                                                                       \
+            if ((M_) == 19) lp_stage1<2>(*dma);                                                                       \
+            if ((M_) == 27) lp_stage1<3>(*dma);                                                                       \
         }                                                                                                             \
         LQ_SM(M_);                                                                                                    \
         __builtin_amdgcn_sched_barrier(0);                                                                            \
     } while (0)
     if (DO_QK && PRE != 2) {
         LQ_READ(0); LQ_READ(1); LQ_READ(2); LQ_READ(3);
-        if (LQ_AHEAD > 4) { LQ_READ(4); }
-        if (LQ_AHEAD > 5) { LQ_READ(5); }
-        if (LQ_AHEAD > 6) { LQ_READ(6); }
     }
     if (!DO_QK) {
         LQ_READ(8); LQ_READ(9); LQ_READ(10); LQ_READ(11);
-        if (LQ_AHEAD > 4) { LQ_READ(12); }
-        if (LQ_AHEAD > 5) { LQ_READ(13); }
-        if (LQ_AHEAD > 6) { LQ_READ(14); }
     }
     __builtin_amdgcn_sched_barrier(0);
     LQ_SLOT(0); LQ_SLOT(1); LQ_SLOT(2); LQ_SLOT(3); LQ_SLOT(4); LQ_SLOT(5); LQ_SLOT(6); LQ_SLOT(7);
@@ -244,11 +195,7 @@ __device__ __forceinline__ void lq_bb(LpState& sa, LpState& sb, const unsigned c
 #undef LQ_LGKM
 #undef LQ_SLOT
     if (DO_QK && !DO_PV) lp_qk_settle();
-    if (DO_SM && LQ_X_NOSM) {
-        pnA[0] = pnA[1] = pnB[0] = pnB[1] = make_uint4(0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u);
-        sa.l += 32.f;
-        sb.l += 32.f;
-    } else if (DO_SM) {
+    if (DO_SM) {
         const auto swA = __builtin_amdgcn_permlane32_swap(__float_as_uint(halfA), __float_as_uint(halfA), false, false);
         const auto swB = __builtin_amdgcn_permlane32_swap(__float_as_uint(halfB), __float_as_uint(halfB), false, false);
         float psumA = __uint_as_float(swA[0]) + __uint_as_float(swA[1]);   // both half-lanes: the row's 32 keys
@@ -481,10 +428,8 @@ __device__ __forceinline__ void attn_pair_lq(const LqParams& P, unsigned char* s
             lq_bb<T, TEXT, 1, true, true, true, ((1 + (J_)) % 3) * LP_TILE, ((J_) % 3) * LP_TILE, 2>(                 \
                 sa, sb, smem, smem, sYa, sYb, sXa, sXb, pYa, pYb, pXa, pXb, k_addr, v_addr, P.qk_scale, frk, &dk_);   \
         }                                                                                                             \
-        if (!LQ_X_NOBAR) {                                                                                            \
-            LQ_WAIT_KEEP8();                                                                                          \
-            __syncthreads();                                                                                          \
-        }                                                                                                             \
+        LQ_WAIT_KEEP8();                                                                                              \
+        __syncthreads();                                                                                              \
     } while (0)
         if (t_fast > 0) {
             LQ_STEP(0, false, false);
@@ -604,14 +549,6 @@ __global__ void __launch_bounds__(LQ_THREADS, 1) bsattn_lq_kernel(LqParams P) {
     attn_pair_lq<T, false>(P, smem, bh / P.H, bh % P.H, 2 * pr, 2 * pr + 1 < P.nq_img, list, n_sh, n_a, n_b);
 }
 
-template <typename T, int VARIANT>
-static hipError_t lq_launch(const LqParams& P, long long grid, hipStream_t stream) {
-    static bool smem_set[64] = {};
-    lp_set_smem_once((const void*)bsattn_lq_kernel<T, VARIANT>, LQ_LDS_BYTES, smem_set);
-    hipLaunchKernelGGL((bsattn_lq_kernel<T, VARIANT>), dim3((unsigned)grid), dim3(LQ_THREADS), LQ_LDS_BYTES, stream, P);
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------------ list merge
 // One wave per query-block pair: the two ascending kept lists -> [shared | A-only | B-only], each ascending.
 constexpr int MERGE_WORDS = 128;   // up to 4096 kv blocks
@@ -704,32 +641,9 @@ extern "C" int jenga_bsattn_pair_fwd(void* stream, const void* q, const void* k,
                                      int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t o_sb, int64_t o_ss,
                                      int64_t o_sh, float sm_scale, float text_amp, int64_t text_block_start, int dtype,
                                      int flags) {
-    if (!q || !k || !vt || !o || B <= 0 || H <= 0 || n_blocks <= 0 || nq_img < 0 || nq_img > n_blocks) {
-        set_error("jenga_bsattn_pair_fwd: bad arguments");
-        return JENGA_EINVAL;
-    }
-    if (nq_img > 0 && (!pidx || !pcnt)) {
-        set_error("jenga_bsattn_pair_fwd: pidx/pcnt are required when nq_img > 0");
-        return JENGA_EINVAL;
-    }
-    const int64_t strides[9] = {q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, o_sb, o_ss, o_sh};
-    for (int i = 0; i < 9; ++i)
-        if (strides[i] & 7) {
-            set_error("jenga_bsattn_pair_fwd: strides must be multiples of 8 elements (16-byte rows)");
-            return JENGA_EINVAL;
-        }
-    if (((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)vt & 15) || ((uintptr_t)o & 15)) {
-        set_error("jenga_bsattn_pair_fwd: pointers must be 16-byte aligned");
-        return JENGA_EINVAL;
-    }
-    if (dtype != JENGA_BF16 && dtype != JENGA_FP16) {
-        set_error("jenga_bsattn_pair_fwd: dtype must be bf16 or fp16");
-        return JENGA_EUNSUPPORTED;
-    }
-    if (k_ss < 0 || k_ss >= (1LL << 31)) {
-        set_error("jenga_bsattn_pair_fwd: k token stride %lld out of range", (long long)k_ss);
-        return JENGA_EINVAL;
-    }
+    const AttnArgs a = {(hipStream_t)stream, q, k, vt, o, seqlens, pidx, pcnt, order, B, H, n_blocks, nq_img, q_sb, q_ss, q_sh,
+                        k_sb, k_ss, k_sh, o_sb, o_ss, o_sh, sm_scale, text_amp, text_block_start, dtype, flags};
+    if (const int rc = attn_check_args("jenga_bsattn_pair_fwd", a, "pidx/pcnt", 0, (1LL << 31) - 1, "k token")) return rc;
     LqParams P;
     P.q = (const uint16_t*)q;
     P.k = (const uint16_t*)k;
@@ -739,64 +653,20 @@ extern "C" int jenga_bsattn_pair_fwd(void* stream, const void* q, const void* k,
     P.pidx = pidx;
     P.pcnt = pcnt;
     P.order = order;
-    P.q_sb = q_sb; P.q_ss = q_ss; P.q_sh = q_sh;
-    P.k_sb = k_sb; P.k_ss = k_ss; P.k_sh = k_sh;
-    P.o_sb = o_sb; P.o_ss = o_ss; P.o_sh = o_sh;
-    P.B = (int)B; P.H = (int)H; P.n_blocks = (int)n_blocks; P.nq_img = (int)nq_img;
+    attn_fill_geom(P, a);
     P.npair_img = (int)((nq_img + 1) / 2);
-    const long long n_text = n_blocks - nq_img;
-    P.npair_txt = (int)((n_text + 1) / 2);
-    P.text_block_start = (int)text_block_start;
-    P.qk_scale = (float)((double)sm_scale * 1.44269504);
-    P.text_amp = text_amp;
+    P.npair_txt = (int)((n_blocks - nq_img + 1) / 2);
     P.bal_set = 0;
-    const long long n_text_wg = B * H * (long long)P.npair_txt;
-    P.n_text_wg_pad = (int)((n_text_wg + 7) / 8 * 8);
-    if ((flags & JENGA_ATTN_XCD_REMAP) && P.npair_img >= 64) {
-        P.xcd_chunk = (P.npair_img + 7) / 8;
-        P.img_per_head = P.xcd_chunk * 8;
-    } else {
-        P.xcd_chunk = 0;
-        P.img_per_head = P.npair_img;
-    }
-    const long long grid = (long long)P.n_text_wg_pad + B * H * (long long)P.img_per_head;
-    if (grid <= 0 || grid > 0x7fffffffLL) {
-        set_error("jenga_bsattn_pair_fwd: grid size %lld out of range", grid);
-        return JENGA_EINVAL;
-    }
-    if (flags & JENGA_ATTN_BALANCE) {      // (per-device state ordered by events: a capturing stream gets the static launch)
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) {
-            (void)hipGetLastError();
-            cap = hipStreamCaptureStatusActive;
-        }
-        if (cap != hipStreamCaptureStatusNone) flags &= ~JENGA_ATTN_BALANCE;
-    }
-    long long grid_bal = 0;
-    int bal_slot = -1;
-    if ((flags & JENGA_ATTN_BALANCE) && P.xcd_chunk && (P.n_text_wg_pad & 7) == 0 && (P.img_per_head & 7) == 0) {
-        const long long img = B * H * (long long)P.img_per_head;
-        long long extra = ((img * lp_balance_extra_pct() / 100) + 7) & ~7LL;
-        extra = extra < 8 ? 8 : extra;
-        if (grid + extra <= 0x7fffffffLL && B * H * (long long)P.xcd_chunk < (1LL << 28)) {
-            bal_slot = lp_balance_acquire((hipStream_t)stream);
-            if (bal_slot >= 0) {
-                grid_bal = grid + extra;
-                P.bal_set = bal_slot;
-            }
-        }
-    }
+    long long grid = attn_plan_grid("jenga_bsattn_pair_fwd", P, B * H, P.npair_txt, P.npair_img, flags);
+    if (!grid) return JENGA_EINVAL;
+    const int bal_slot = lp_balance_plan(a.stream, flags, P, B * H, &grid);
     hipError_t e;
-    if (grid_bal)
-        e = dtype == JENGA_BF16 ? lq_launch<BF16, 4>(P, grid_bal, (hipStream_t)stream)
-                                : lq_launch<FP16, 4>(P, grid_bal, (hipStream_t)stream);
-    else
-        e = dtype == JENGA_BF16 ? lq_launch<BF16, 0>(P, grid, (hipStream_t)stream)
-                                : lq_launch<FP16, 0>(P, grid, (hipStream_t)stream);
-    if (bal_slot >= 0) lp_balance_release(bal_slot, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        set_error("jenga_bsattn_pair_fwd: %s", hipGetErrorString(e));
-        return JENGA_ELAUNCH;
+    if (bal_slot >= 0) {
+        P.bal_set = bal_slot;
+        e = ATTN_LAUNCH_V(dtype, bsattn_lq_kernel, 4, LQ_LDS_BYTES, P, grid, a.stream);
+        lp_balance_release(bal_slot, a.stream);
+    } else {
+        e = ATTN_LAUNCH_V(dtype, bsattn_lq_kernel, 0, LQ_LDS_BYTES, P, grid, a.stream);
     }
-    return JENGA_OK;
+    return attn_launch_result("jenga_bsattn_pair_fwd", e);
 }

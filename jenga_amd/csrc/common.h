@@ -81,6 +81,19 @@ __host__ __device__ __forceinline__ int pv_key_of_pos(int p) {
     return (r & 3) + 8 * (r >> 2) + 4 * hi;
 }
 
+// What the block-sparse attention kernels (bsattn.hip, bsattn3.hip, bsattn5.hip, qattn.hip) share of their launch
+// parameters: strides in elements, sizes, the score constants and the grid layout.  Filled on the host (attn_launch.h).
+struct AttnGeom {
+    long long q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, o_sb, o_ss, o_sh;
+    int B, H, n_blocks, nq_img;
+    int text_block_start;
+    float qk_scale;     // sm_scale * log2(e), fp32
+    float text_amp;
+    int n_text_wg_pad;  // text workgroups (padded to a multiple of 8) come first in the grid
+    int img_per_head;   // grid slots per (b, h) for image items (8 C with XCD remap, the item count otherwise)
+    int xcd_chunk;      // C, or 0 = plain order
+};
+
 void set_error(const char* fmt, ...);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per kernel instantiation and device: `done` is a static of the
@@ -96,10 +109,3 @@ inline void lp_set_smem_once(const void* kernel, int bytes, bool (&done)[64]) {
 }
 
 }  // namespace jenga
-
-// bsattn3.hip: the launcher behind jenga_bsattn_fwd(..., flags & JENGA_ATTN_LP); arguments already validated
-int jenga_bsattn_lp_launch(void* stream, const void* q, const void* k, const void* vt, void* o, const int32_t* seqlens,
-                           const int32_t* idx, const int32_t* cnt, const int32_t* order, int64_t B, int64_t H,
-                           int64_t n_blocks, int64_t nq_img, int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t k_sb,
-                           int64_t k_ss, int64_t k_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh, float sm_scale,
-                           float text_amp, int64_t text_block_start, int dtype, int flags);

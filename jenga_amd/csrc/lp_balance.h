@@ -147,5 +147,29 @@ inline int lp_balance_extra_pct() {
     return pct;
 }
 
+// Host side of a launch with JENGA_ATTN_BALANCE in `flags`, given its grid layout (`bh` heads): -> the counter set the
+// launch draws from, with *grid grown by the oversubscription (JENGA_BALANCE_EXTRA_PCT of the image slots, at least 8
+// workgroups, so that a fast XCD has workgroups left to draw from a slow one's queue) -- the caller launches its balanced
+// instantiation and then calls lp_balance_release; or -1 with *grid untouched: the plain static launch.
+template <typename G>   // G: the launch's grid layout (xcd_chunk, n_text_wg_pad, img_per_head)
+int lp_balance_plan(hipStream_t stream, int flags, const G& g, long long bh, long long* grid) {
+    if (!(flags & JENGA_ATTN_BALANCE)) return -1;
+    // the per-device state is ordered by events: that cannot be recorded into a HIP graph, so a capturing stream gets the
+    // static launch
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cap) != hipSuccess) {
+        (void)hipGetLastError();      // (the query itself failed: not this launch's error)
+        cap = hipStreamCaptureStatusActive;
+    }
+    if (cap != hipStreamCaptureStatusNone) return -1;
+    if (!g.xcd_chunk || (g.n_text_wg_pad & 7) != 0 || (g.img_per_head & 7) != 0) return -1;
+    long long extra = ((bh * g.img_per_head * lp_balance_extra_pct() / 100) + 7) & ~7LL;
+    extra = extra < 8 ? 8 : extra;
+    if (*grid + extra > 0x7fffffffLL || bh * g.xcd_chunk >= (1LL << 28)) return -1;   // (a ticket is queue << 28 | position)
+    const int set = lp_balance_acquire(stream);
+    if (set >= 0) *grid += extra;
+    return set;
+}
+
 }  // namespace
 }  // namespace jenga

@@ -23,7 +23,7 @@
 // (vmcnt(2) leaves the K8 pieces of tile t + 2 in flight), one barrier per tile.
 #include <math.h>
 
-#include "common.h"
+#include "attn_launch.h"
 
 namespace jenga {
 namespace {
@@ -115,14 +115,7 @@ struct QaParams {
     const int32_t* seqlens;
     const int32_t* idx;
     const int32_t* cnt;
-    long long q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, o_sb, o_ss, o_sh;
-    int B, H, n_blocks, nq_img;
-    int text_block_start;
-    float qk_scale;   // sm_scale * log2(e)
-    float text_amp;
-    int n_text_wg_pad;  // text workgroups (padded to a multiple of 8) come first in the grid
-    int img_per_head;   // grid slots per (b, h) for image blocks (8 C with XCD remap, nq_img otherwise)
-    int xcd_chunk;      // C, or 0 = plain order
+    AttnGeom g;   // strides of q8 / k8 in bytes
 };
 
 constexpr int QA_KT = 64;                        // keys per LDS tile
@@ -176,28 +169,28 @@ __device__ __forceinline__ void qa_block(const QaParams& P, unsigned char* smem,
     const int lane = tid & 63;
     const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lq = lane & 31, hi = lane >> 5;
-    const int seqlen = P.seqlens ? P.seqlens[b] : P.n_blocks * 128;
-    const long long bh = (long long)b * P.H + h;
+    const int seqlen = P.seqlens ? P.seqlens[b] : P.g.n_blocks * 128;
+    const long long bh = (long long)b * P.g.H + h;
 
     // ---- kept-block list ----
     const int32_t* list = nullptr;
     int nkept;
     if (TEXT) {
-        nkept = P.n_blocks;
+        nkept = P.g.n_blocks;
     } else {
-        const long long row = bh * P.nq_img + m;
-        list = P.idx + row * P.n_blocks;
+        const long long row = bh * P.g.nq_img + m;
+        list = P.idx + row * P.g.n_blocks;
         nkept = __builtin_amdgcn_readfirstlane(P.cnt[row]);
-        nkept = nkept < 0 ? 0 : (nkept > P.n_blocks ? P.n_blocks : nkept);
+        nkept = nkept < 0 ? 0 : (nkept > P.g.n_blocks ? P.g.n_blocks : nkept);
     }
-    const float* const ksc = P.k_scale + bh * P.n_blocks;
-    const float sc_q = P.q_scale[bh * P.n_blocks + m] * P.qk_scale;
+    const float* const ksc = P.k_scale + bh * P.g.n_blocks;
+    const float sc_q = P.q_scale[bh * P.g.n_blocks + m] * P.g.qk_scale;
 
     // ---- Q8 fragments: lane (lq, hi) keeps channels 64 j + 32 hi .. + 31 of its row for MFMA j ----
     const long long qrow = (long long)m * 128 + wave_u * 32 + lq;
     qa_i8 qf[2];
     {
-        const unsigned char* qp = P.q8 + b * P.q_sb + qrow * P.q_ss + h * P.q_sh + hi * 32;
+        const unsigned char* qp = P.q8 + b * P.g.q_sb + qrow * P.g.q_ss + h * P.g.q_sh + hi * 32;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const uint4 a = *reinterpret_cast<const uint4*>(qp + j * 64);
@@ -205,7 +198,7 @@ __device__ __forceinline__ void qa_block(const QaParams& P, unsigned char* smem,
             qf[j] = qa_i8{(int)a.x, (int)a.y, (int)a.z, (int)a.w, (int)c.x, (int)c.y, (int)c.z, (int)c.w};
         }
     }
-    uint16_t* const op = P.o + b * P.o_sb + qrow * P.o_ss + h * P.o_sh + hi * 4;
+    uint16_t* const op = P.o + b * P.g.o_sb + qrow * P.g.o_ss + h * P.g.o_sh + hi * 4;
 
     f32x16 oacc[4];
 #pragma unroll
@@ -218,8 +211,8 @@ __device__ __forceinline__ void qa_block(const QaParams& P, unsigned char* smem,
 #pragma unroll
     for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
 
-    const unsigned char* kbh = P.k8 + b * P.k_sb + h * P.k_sh;
-    const uint16_t* vbh = P.vt + bh * (long long)P.n_blocks * 2 * (128 * QA_KT);
+    const unsigned char* kbh = P.k8 + b * P.g.k_sb + h * P.g.k_sh;
+    const uint16_t* vbh = P.vt + bh * (long long)P.g.n_blocks * 2 * (128 * QA_KT);
 
     // ---- loop-invariant LDS read addresses ----
     int k_addr[4], v_addr[4];   // K8: chunk c = 4 j + 2 hi + e of key lq, index 2 j + e
@@ -235,7 +228,7 @@ __device__ __forceinline__ void qa_block(const QaParams& P, unsigned char* smem,
     const unsigned smem_base =
         __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem);
     const int pr_ = lane >> 3, pc_ = lane & 7, psw_ = lane >> 4;
-    const unsigned kss_b = (unsigned)P.k_ss;   // 64 rows x stride < 2^31, checked on the host
+    const unsigned kss_b = (unsigned)P.g.k_ss;   // 64 rows x stride < 2^31, checked on the host
     const unsigned k_src0 = (unsigned)(16 * wave_u + pr_) * kss_b + ((pc_ ^ psw_) << 4);
     const unsigned k_src1 = (unsigned)(16 * wave_u + 8 + pr_) * kss_b + ((pc_ ^ (4 + psw_)) << 4);
     const int vr_ = 32 * wave_u + pr_;
@@ -251,7 +244,7 @@ __device__ __forceinline__ void qa_block(const QaParams& P, unsigned char* smem,
         for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(qf[j][i]));
 
     auto stage = [&](int kblk, int khalf, int vblk, int vhalf, int kslot, int vslot) {
-        qa_stage(kbh + ((long long)kblk * 128 + khalf * QA_KT) * P.k_ss, vbh + ((long long)vblk * 2 + vhalf) * (128 * QA_KT),
+        qa_stage(kbh + ((long long)kblk * 128 + khalf * QA_KT) * P.g.k_ss, vbh + ((long long)vblk * 2 + vhalf) * (128 * QA_KT),
                  smem_base + kslot * QA_K_TILE + wave_u * 2048, smem_base + QA_V_RING + vslot * QA_V_TILE + wave_u * 4096,
                  k_src0, k_src1, v_src0, v_src1, v_src2, v_src3);
     };
@@ -277,7 +270,7 @@ __device__ __forceinline__ void qa_block(const QaParams& P, unsigned char* smem,
             s1 = mfma_fp8(kb[2], kb[3], qf[1], s1);
             __builtin_amdgcn_s_setprio(0);
         }
-        const float amp = (!TEXT && blk >= P.text_block_start) ? P.text_amp : 0.f;
+        const float amp = (!TEXT && blk >= P.g.text_block_start) ? P.g.text_amp : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             s0[r] = fmaf(s0[r], sc, amp);
@@ -351,7 +344,7 @@ __device__ __forceinline__ void qa_block(const QaParams& P, unsigned char* smem,
             int e = j + lane;
             if (!TEXT) {
                 e = e < nkept ? list[e] : 0;
-                e = e < 0 ? 0 : (e >= P.n_blocks ? P.n_blocks - 1 : e);   // whatever the list holds: inside the tensors
+                e = e < 0 ? 0 : (e >= P.g.n_blocks ? P.g.n_blocks - 1 : e);   // whatever the list holds: inside the tensors
             } else {
                 e = e < nkept ? e : 0;
             }
@@ -416,34 +409,26 @@ __device__ __forceinline__ void qa_block(const QaParams& P, unsigned char* smem,
 template <typename T>
 __global__ void __launch_bounds__(256, 2) bsattn_fp8_kernel(QaParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int n_text = P.n_blocks - P.nq_img;
+    const int n_text = P.g.n_blocks - P.g.nq_img;
     const int id = blockIdx.x;
-    if (id < P.n_text_wg_pad) {   // text query blocks first: the longest work items start earliest
-        if (id >= P.B * P.H * n_text) return;
-        const int m = P.nq_img + id % n_text;
+    if (id < P.g.n_text_wg_pad) {   // text query blocks first: the longest work items start earliest
+        if (id >= P.g.B * P.g.H * n_text) return;
+        const int m = P.g.nq_img + id % n_text;
         const int bh = id / n_text;
-        qa_block<T, true>(P, smem, bh / P.H, bh % P.H, m);
+        qa_block<T, true>(P, smem, bh / P.g.H, bh % P.g.H, m);
         return;
     }
-    const int li = id - P.n_text_wg_pad;
-    const int bh = li / P.img_per_head;
-    const int r = li % P.img_per_head;
+    const int li = id - P.g.n_text_wg_pad;
+    const int bh = li / P.g.img_per_head;
+    const int r = li % P.g.img_per_head;
     int m;
-    if (P.xcd_chunk) {   // workgroup id -> XCD is id % 8: give each XCD a contiguous range of query blocks
-        m = (r & 7) * P.xcd_chunk + (r >> 3);
-        if ((r >> 3) >= P.xcd_chunk || m >= P.nq_img) return;
+    if (P.g.xcd_chunk) {   // workgroup id -> XCD is id % 8: give each XCD a contiguous range of query blocks
+        m = (r & 7) * P.g.xcd_chunk + (r >> 3);
+        if ((r >> 3) >= P.g.xcd_chunk || m >= P.g.nq_img) return;
     } else {
         m = r;
     }
-    qa_block<T, false>(P, smem, bh / P.H, bh % P.H, m);
-}
-
-template <typename T>
-hipError_t qa_launch(const QaParams& P, unsigned grid, hipStream_t stream) {
-    static bool attr_done[64] = {};
-    lp_set_smem_once(reinterpret_cast<const void*>(&bsattn_fp8_kernel<T>), QA_LDS_BYTES, attr_done);
-    hipLaunchKernelGGL(bsattn_fp8_kernel<T>, dim3(grid), dim3(256), QA_LDS_BYTES, stream, P);
-    return hipGetLastError();
+    qa_block<T, false>(P, smem, bh / P.g.H, bh % P.g.H, m);
 }
 
 bool bad16(const void* p) { return ((uintptr_t)p & 15) != 0; }
@@ -508,36 +493,18 @@ extern "C" int jenga_bsattn_fp8_fwd(void* stream, const void* q8, const float* q
         set_error("jenga_bsattn_fp8_fwd: sm_scale must be positive and finite");
         return JENGA_EINVAL;
     }
+    const AttnArgs a = {(hipStream_t)stream, q8, k8, vt, o, seqlens, idx, cnt, nullptr, B, H, n_blocks, nq_img, q_sb, q_ss, q_sh,
+                        k_sb, k_ss, k_sh, o_sb, o_ss, o_sh, sm_scale, text_amp, text_block_start, dtype, flags};
     QaParams P;
     P.q8 = (const unsigned char*)q8; P.k8 = (const unsigned char*)k8; P.q_scale = q_scale; P.k_scale = k_scale;
     P.vt = (const uint16_t*)vt; P.o = (uint16_t*)o;
     P.seqlens = seqlens; P.idx = idx; P.cnt = cnt;
-    P.q_sb = q_sb; P.q_ss = q_ss; P.q_sh = q_sh;
-    P.k_sb = k_sb; P.k_ss = k_ss; P.k_sh = k_sh;
-    P.o_sb = o_sb; P.o_ss = o_ss; P.o_sh = o_sh;
-    P.B = (int)B; P.H = (int)H; P.n_blocks = (int)n_blocks; P.nq_img = (int)nq_img;
-    P.text_block_start = (int)(text_block_start < 0 ? 0 : (text_block_start > n_blocks ? n_blocks : text_block_start));
-    P.qk_scale = (float)((double)sm_scale * 1.4426950408889634);
-    P.text_amp = text_amp;
-    const long long n_text_wg = B * H * (n_blocks - nq_img);
-    P.n_text_wg_pad = (int)((n_text_wg + 7) / 8 * 8);
-    if ((flags & JENGA_ATTN_XCD_REMAP) && nq_img >= 64) {
-        P.xcd_chunk = (int)((nq_img + 7) / 8);
-        P.img_per_head = P.xcd_chunk * 8;
-    } else {
-        P.xcd_chunk = 0;
-        P.img_per_head = (int)nq_img;
-    }
-    const long long grid = (n_text_wg + 7) / 8 * 8 + B * H * (long long)P.img_per_head;
-    if (grid <= 0 || grid > 0x7fffffffLL) {
-        set_error("jenga_bsattn_fp8_fwd: grid size %lld out of range", grid);
-        return JENGA_EINVAL;
-    }
-    const hipError_t e = dtype == JENGA_BF16 ? qa_launch<BF16>(P, (unsigned)grid, (hipStream_t)stream)
-                                             : qa_launch<FP16>(P, (unsigned)grid, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        set_error("jenga_bsattn_fp8_fwd: %s", hipGetErrorString(e));
-        return JENGA_ELAUNCH;
-    }
-    return JENGA_OK;
+    attn_fill_geom(P.g, a);
+    // this kernel's own: the list entries index the scale arrays, so text_block_start is clamped; log2(e) to full precision
+    P.g.text_block_start = (int)(text_block_start < 0 ? 0 : (text_block_start > n_blocks ? n_blocks : text_block_start));
+    P.g.qk_scale = (float)((double)sm_scale * 1.4426950408889634);
+    const long long grid = attn_plan_grid("jenga_bsattn_fp8_fwd", P.g, B * H, n_blocks - nq_img, nq_img, flags);
+    if (!grid) return JENGA_EINVAL;
+    return attn_launch_result("jenga_bsattn_fp8_fwd",
+                              ATTN_LAUNCH(dtype, bsattn_fp8_kernel, QA_LDS_BYTES, P, grid, a.stream));
 }

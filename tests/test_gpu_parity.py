@@ -731,6 +731,48 @@ def test_c_abi_rejects_bad_arguments_on_device(dev):
     bad = list(args())
     bad[6] = None
     assert L.jenga_bsattn_fwd(*bad) != 0 and b"idx" in L.jenga_last_error()
+
+    # the other attention entries, same shapes (B = 1, H = 1, two blocks): one accepted call each, then the same kinds of bad
+    # argument -- rejected under the entry's own name
+    def rejected(fn, name, a):
+        assert fn(*a) != 0, name
+        assert L.jenga_last_error().startswith(name.encode()), (name, L.jenga_last_error())
+
+    def without(a, i):
+        a = list(a)
+        a[i] = None
+        return a
+
+    pidx = torch.zeros(1, 1, 1, 2, dtype=torch.int32, device=dev)
+    pcnt = torch.tensor([1, 0, 0, 0], dtype=torch.int32, device=dev).view(1, 1, 1, 4)    # one shared kv block
+    pargs = lambda qq=q, dtype=0, ss=128: (st, p(qq), p(q), p(vt), p(o), p(sl), p(pidx), p(pcnt), None, 1, 1, 2, 2, 256 * 128,
+                                           ss, 128, 256 * 128, 128, 128, 256 * 128, 128, 128, 0.088, 0.0, 2, dtype, 1)
+    assert L.jenga_bsattn_pair_fwd(*pargs()) == 0, L.jenga_last_error()
+    torch.cuda.synchronize()
+    rejected(L.jenga_bsattn_pair_fwd, "jenga_bsattn_pair_fwd", pargs(dtype=7))
+    rejected(L.jenga_bsattn_pair_fwd, "jenga_bsattn_pair_fwd", pargs(ss=129))
+    rejected(L.jenga_bsattn_pair_fwd, "jenga_bsattn_pair_fwd", pargs(qq=q_mis))
+    rejected(L.jenga_bsattn_pair_fwd, "jenga_bsattn_pair_fwd", without(pargs(), 6))
+
+    xargs = lambda qq=q, dtype=0, ss=128: (st, p(qq), p(q), p(vt), p(o), 1, 1, 2, 2, 256, 256 * 128, ss, 128, 256 * 128, 128,
+                                           128, 256 * 128, 128, 128, 0.088, dtype)
+    assert L.jenga_cross_attn_fwd(*xargs()) == 0, L.jenga_last_error()
+    torch.cuda.synchronize()
+    rejected(L.jenga_cross_attn_fwd, "jenga_cross_attn_fwd", xargs(dtype=7))
+    rejected(L.jenga_cross_attn_fwd, "jenga_cross_attn_fwd", xargs(ss=129))
+    rejected(L.jenga_cross_attn_fwd, "jenga_cross_attn_fwd", xargs(qq=q_mis))     # (no lists in this entry)
+
+    q8 = torch.zeros(1, 256, 1, 128, device=dev, dtype=torch.uint8)
+    q8_mis = torch.zeros(256 * 128 + 16, device=dev, dtype=torch.uint8)[8:]
+    sc8 = torch.ones(1, 1, 2, device=dev, dtype=torch.float32)
+    fargs = lambda qq=q8, dtype=0, ss=128: (st, p(qq), p(sc8), p(q8), p(sc8), p(vt), p(o), p(sl), p(idx), p(cnt), 1, 1, 2, 2,
+                                            256 * 128, ss, 128, 256 * 128, 128, 128, 256 * 128, 128, 128, 0.088, 0.0, 2, dtype, 1)
+    assert L.jenga_bsattn_fp8_fwd(*fargs()) == 0, L.jenga_last_error()
+    torch.cuda.synchronize()
+    rejected(L.jenga_bsattn_fp8_fwd, "jenga_bsattn_fp8_fwd", fargs(dtype=7))
+    rejected(L.jenga_bsattn_fp8_fwd, "jenga_bsattn_fp8_fwd", fargs(ss=136))      # q8 / k8 strides: multiples of 16
+    rejected(L.jenga_bsattn_fp8_fwd, "jenga_bsattn_fp8_fwd", fargs(qq=q8_mis))
+    rejected(L.jenga_bsattn_fp8_fwd, "jenga_bsattn_fp8_fwd", without(fargs(), 8))
     # host wrapper: one kv length per sample is required (the reference would read past cu_seqlens_q[1:2] for B = 2)
     q2 = torch.zeros(2, 256, 1, 128, device=dev, dtype=torch.bfloat16)
     vt2 = torch.zeros(2, 1, 4, 128, 64, device=dev, dtype=torch.bfloat16)

@@ -120,8 +120,8 @@ def test_lds_dma_always_follows_an_m0_write_of_its_own_stretch(asm, asm_pair):
     """LDS-DMA takes its LDS base from M0, which the helpers of lp_core.h write in their own asm statements.  The lint
     (tools/isa_hazards.py::check_m0) walks the generated code of both attention kernels: every global_load_lds follows an
     `s_mov_b32 m0` of the same straight-line stretch, nothing else writes M0 in between, and a wait state separates the two.
-    (It is what makes the LP_DMA_M0_ONCE form -- one M0 write per four-piece stage, round 6, profiles/r06_attn_pair_diet.json --
-    checkable at all; the product build writes M0 per piece and must pass as well.)  A hand-made violation is caught."""
+    (The kernels write M0 in front of every piece; the form with one M0 write per four-piece stage was measured in round 6,
+    profiles/r06_attn_pair_diet.json, and is no longer in the source.)  A hand-made violation is caught."""
     import isa_hazards as Hz
     import isa_loop_spills as T
     for text, pat in ((asm, "bsattn_lp_kernel"), (asm_pair, "bsattn_lq_kernel")):

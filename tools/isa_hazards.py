@@ -79,8 +79,8 @@ def check(lines, need=2, far=20):
 
 
 def check_m0(lines):
-    """LDS-DMA (global_load_lds_*) takes its LDS base from M0.  With LP_DMA_M0_ONCE (lp_core.h) only the first piece of a
-    four-piece stage writes M0; the other three rely on it.  Per straight-line stretch (labels are join points: M0 unknown
+    """LDS-DMA (global_load_lds_*) takes its LDS base from M0, which the staging helpers of lp_core.h write in front of
+    every piece (a stage whose later pieces rely on the first one's write passes too).  Per straight-line stretch (labels are join points: M0 unknown
     behind them): every global_load_lds must follow an `s_mov_b32 m0, ...` of the same stretch with no other write to M0 in
     between, and at least one wait state behind that s_mov.  -> list of (index, line, reason)"""
     bad, valid, since = [], False, 0
