@@ -14,9 +14,11 @@
  *   - return value: JENGA_OK or an error code; jenga_last_error() gives the message for this thread.
  *   - the kernels work on 128-channel rows and 128-token blocks (the only configuration the reference runs: HunyuanVideo,
  *     HunyuanVideo-I2V, Wan2.1 all use D=128 and BLOCK_M=BLOCK_N=128).  The Triton kernel's other accepted head dims
- *     (16 / 32 / 64, ...diffres.py:155) are served by the host side on the same entry points: rows zero-padded to 128
- *     channels, the true head_dim ** -0.5 passed as sm_scale (jenga_bsattn_fwd) and as JENGA_SELECT_HEAD_DIM(d)
- *     (jenga_block_select) -- exact zeros in every dot product (jenga_amd/modules/attention_block_sparse.py).
+ *     (16 / 32 / 64, ...diffres.py:155): 64-channel rows have entry points of their own, jenga_block_pool_d64 and
+ *     jenga_bsattn_d64_fwd, which take the tensors as they lie in memory (narrow_heads="native" in
+ *     jenga_amd/modules/attention_block_sparse.py); by default, and for 16 / 32 channels always, the host side serves them on
+ *     the 128-channel entry points: rows zero-padded to 128 channels, the true head_dim ** -0.5 passed as sm_scale
+ *     (jenga_bsattn_fwd) and as JENGA_SELECT_HEAD_DIM(d) (jenga_block_select) -- exact zeros in every dot product.
  *   - state the library keeps (everything else is a pure function of its arguments):
  *       a thread-local error string (jenga_last_error);
  *       per device, for launches with JENGA_ATTN_BALANCE: 64 sets of 8 ticket counters in device memory, an event per
@@ -400,6 +402,36 @@ int jenga_bsattn_fp8_fwd(void* stream, const void* q8, const float* q_scale, con
                          int64_t H, int64_t n_blocks, int64_t nq_img, int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t k_sb,
                          int64_t k_ss, int64_t k_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh, float sm_scale,
                          float text_amp, int64_t text_block_start, int dtype, int flags);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Block-sparse attention on 64-channel heads (csrc/bsattn64.hip; additive exports inside ABI 4).  The reference's Triton kernel
+ * accepts head dim 64 (attention_block_triton_diffres.py:155); these two entries run it without zero-padding the rows to 128
+ * channels, without a jenga_pack_v workspace and without slicing the output.
+ *
+ * jenga_block_pool_d64: x [B, S, H, 64] strided (strides multiples of 8 elements, x 16-byte aligned), n_blocks*128 <= S ->
+ *   pooled [B, H, n_blocks, 128] contiguous in dtype: channels 0..63 the block means, channels 64..127 zeros -- bit-identical
+ *   to jenga_block_pool of the zero-padded rows (8 tokens per thread summed in fp32, the 16 partial sums added in ascending
+ *   order, s / 128.0f, one rounding), so jenga_block_select with JENGA_SELECT_HEAD_DIM(64) takes it unchanged.
+ * jenga_bsattn_d64_fwd: the semantics of jenga_bsattn_fwd on q, k, v, o [B, S, H, 64] strided (S = n_blocks*128, every stride
+ *   a multiple of 8 elements, pointers 16-byte aligned, anything else: JENGA_EINVAL), seqlens int32 [B] on the device or NULL
+ *   (= S).  V is read as it lies in memory: there is no packing step and no workspace.
+ *   image query blocks m < nq_img use idx / cnt (layout of jenga_block_select, row stride n_blocks; entries are clamped into
+ *   [0, n_blocks), counts into [0, n_blocks]; both may be NULL when nq_img == 0):
+ *       q~ = dtype(float(q) * (sm_scale*log2 e)); s = q~.k^T (fp32, base 2) [+ text_amp if kv block >= text_block_start];
+ *       kv columns >= seqlens[b] are -inf, a 64-key tile wholly behind seqlens[b] is not read; online softmax; P rounded to
+ *       dtype before P.V; the row sum taken from the unrounded p; o = acc / l, one rounding.  Rows >= seqlens[b] (and rows
+ *       without a single valid kept key) are written as zeros.
+ *   text query blocks m >= nq_img attend to every kv block: unrounded q, softmax(q.k^T * sm_scale), no mask, no text_amp.
+ *   sm_scale > 0 (64 ** -0.5 for the reference's semantics).  flags: 0 or JENGA_ATTN_XCD_REMAP; any other bit:
+ *   JENGA_EUNSUPPORTED.  No `order`.  Deterministic; close to, not bit-equal with, jenga_bsattn_fwd on the padded rows (the
+ *   running maximum is the exact row maximum here, an integer-valued reference there). */
+int jenga_block_pool_d64(void* stream, const void* x, void* pooled, int64_t B, int64_t H, int64_t n_blocks, int64_t x_sb,
+                         int64_t x_ss, int64_t x_sh, int dtype);
+int jenga_bsattn_d64_fwd(void* stream, const void* q, const void* k, const void* v, void* o, const int32_t* seqlens,
+                         const int32_t* idx, const int32_t* cnt, int64_t B, int64_t H, int64_t n_blocks, int64_t nq_img,
+                         int64_t q_sb, int64_t q_ss, int64_t q_sh, int64_t k_sb, int64_t k_ss, int64_t k_sh, int64_t v_sb,
+                         int64_t v_ss, int64_t v_sh, int64_t o_sb, int64_t o_ss, int64_t o_sh, float sm_scale, float text_amp,
+                         int64_t text_block_start, int dtype, int flags);
 
 /* ---------------------------------------------------------------------------------------------------
  * Ulysses head pack/unpack: the local halves of xFuserLongContextAttention.forward's SeqAllToAll4D calls

@@ -63,6 +63,8 @@ SIGNATURES = {
     "jenga_dense_varlen_fwd": (_i32, [_vp] * 7 + [_i64] * 12 + [_f32, _i32]),
     "jenga_quant_fp8_blocks": (_i32, [_vp] * 5 + [_i64] * 6 + [_i32]),
     "jenga_bsattn_fp8_fwd": (_i32, [_vp] * 10 + [_i64] * 13 + [_f32, _f32, _i64, _i32, _i32]),
+    "jenga_block_pool_d64": (_i32, [_vp, _vp, _vp] + [_i64] * 6 + [_i32]),
+    "jenga_bsattn_d64_fwd": (_i32, [_vp] * 8 + [_i64] * 16 + [_f32, _f32, _i64, _i32, _i32]),
     "jenga_linear_export_choices": (_i64, [_vp, _i64]),
     "jenga_linear_import_choices": (_i32, [_vp, _i64]),
     "jenga_linear_import_mismatches": (_i64, []),
@@ -848,6 +850,53 @@ def bsattn_fp8_fwd(q8, q_scale, k8, k_scale, vt, seqlens, idx, cnt, nq_img, sm_s
             prof.per_launch.append((prof.tag, tot))
             if idx is not None and nq_img > 1:
                 prof.last_lists = (idx, cnt)
+    return out
+
+
+def block_pool_d64(x, n_blocks):
+    """x [B,S,H,64] -> [B,H,n_blocks,128]: means over 128-token blocks in channels 0..63, zeros in 64..127 -- what block_pool
+    gives for the zero-padded rows, bit for bit (csrc/bsattn64.hip); block_select(head_dim=64) takes it as it is."""
+    _need_gpu(x, "block_pool_d64")
+    if x.dim() != 4 or x.shape[3] != 64 or n_blocks * 128 > x.shape[1]:
+        raise ValueError("block_pool_d64: x must be [B,S,H,64] with n_blocks*128 <= S")
+    B, S, H, _ = x.shape
+    out = torch.empty((B, H, n_blocks, 128), dtype=x.dtype, device=x.device)
+    with _on(x.device):
+        _check(lib().jenga_block_pool_d64(_stream(x.device), _p(x), _p(out), B, H, n_blocks, *_bshd_strides(x),
+                                          dtype_code(x.dtype)), "jenga_block_pool_d64")
+    return out
+
+
+def bsattn_d64_fwd(q, k, v, seqlens, idx, cnt, nq_img, sm_scale, text_amp, text_block_start, out=None, xcd_remap=True):
+    """bsattn_fwd for 64-channel heads: q, k, v [B,S,H,64] as they lie in memory (unit channel stride, no pack_v workspace),
+    seqlens / idx / cnt as for bsattn_fwd -> o [B,S,H,64] (csrc/bsattn64.hip)."""
+    _need_gpu(q, "bsattn_d64_fwd")
+    if q.dim() != 4 or q.shape[3] != 64 or q.shape[1] % 128 or q.shape[1] == 0:
+        raise ValueError("bsattn_d64_fwd: q must be [B, n*128, H, 64]")
+    B, S, H, _ = q.shape
+    n_blocks = S // 128
+    if out is None:
+        out = torch.empty((B, S, H, 64), dtype=q.dtype, device=q.device)
+    for name, t in (("k", k), ("v", v), ("out", out)):
+        if t.shape != q.shape or t.dtype != q.dtype or t.device != q.device:
+            raise ValueError(f"bsattn_d64_fwd: {name} must have q's shape, dtype and device")
+    if seqlens is not None and (seqlens.dtype != torch.int32 or seqlens.device != q.device):
+        seqlens = seqlens.to(device=q.device, dtype=torch.int32)
+    if seqlens is not None and seqlens.numel() < B:
+        raise ValueError(f"bsattn_d64_fwd: seqlens has {seqlens.numel()} entries for batch {B}")
+    if not 0 <= nq_img <= n_blocks:
+        raise ValueError("bsattn_d64_fwd: nq_img must lie in [0, n_blocks]")
+    if nq_img > 0 and (idx is None or cnt is None or tuple(idx.shape) != (B, H, nq_img, n_blocks)
+                       or tuple(cnt.shape) != (B, H, nq_img) or idx.dtype != torch.int32 or cnt.dtype != torch.int32
+                       or not idx.is_contiguous() or not cnt.is_contiguous() or idx.device != q.device
+                       or cnt.device != q.device):
+        raise ValueError("bsattn_d64_fwd: idx / cnt must be contiguous int32 [B,H,nq_img,n_blocks] / [B,H,nq_img]")
+    with _on(q.device):
+        _check(lib().jenga_bsattn_d64_fwd(_stream(q.device), _p(q), _p(k), _p(v), _p(out), _p(seqlens), _p(idx), _p(cnt),
+                                          B, H, n_blocks, nq_img, *_bshd_strides(q), *_bshd_strides(k), *_bshd_strides(v),
+                                          *_bshd_strides(out), float(sm_scale), float(text_amp), int(text_block_start),
+                                          dtype_code(q.dtype), ATTN_XCD_REMAP if xcd_remap else 0),
+               "jenga_bsattn_d64_fwd")
     return out
 
 

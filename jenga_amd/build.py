@@ -44,6 +44,8 @@ SOURCES = [
     ("dattn.hip", ["-fno-honor-nans", "-Wno-inline-asm"] + NO_PK),
     # the FP8 Q.K kernel and its quantiser: same flags (the quantiser's divisions are __fdiv_rn, its only arithmetic besides)
     ("qattn.hip", ["-fno-honor-nans", "-Wno-inline-asm"] + NO_PK),
+    # the 64-channel block-sparse kernel and its pooling: same flags (the softmax's scalar adds and multiplies are written out)
+    ("bsattn64.hip", ["-fno-honor-nans", "-Wno-inline-asm"] + NO_PK),
 ]
 
 def _hipcc():

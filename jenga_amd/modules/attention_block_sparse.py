@@ -9,6 +9,7 @@ Everything numeric runs in libjenga_amd.so (HIP, gfx950) through jenga_amd._capi
   jenga_block_pool + jenga_block_select  (reference :198-295)   selection -> ascending kept-block lists
   jenga_pack_v + jenga_bsattn_fwd        (reference :38-196, :371-380)   image rows + text rows in one launch
   qk_dtype="fp8" (opt-in, jenga_amd extension): jenga_quant_fp8_blocks on q and k + jenga_bsattn_fp8_fwd in its place
+  narrow_heads="native" (opt-in, head_dim 64): jenga_block_pool_d64 + jenga_bsattn_d64_fwd on the 64-channel rows as given
 torch is used for allocation, views and zero-padding only.  No CPU fallback.
 """
 
@@ -50,6 +51,15 @@ def _check_qk_dtype(qk_dtype, head_dim):
         raise ValueError(f"jenga_amd: qk_dtype='fp8' needs head_dim 128 (got {head_dim})")
 
 
+def _check_narrow_heads(narrow_heads, head_dim, qk_dtype):
+    if narrow_heads not in ("pad", "native"):
+        raise ValueError(f"jenga_amd: narrow_heads must be 'pad' or 'native' (got {narrow_heads!r})")
+    if narrow_heads == "native" and head_dim != 64:
+        raise ValueError(f"jenga_amd: narrow_heads='native' needs head_dim 64 (got {head_dim})")
+    if narrow_heads == "native" and qk_dtype == "fp8":
+        raise ValueError("jenga_amd: narrow_heads='native' cannot be combined with qk_dtype='fp8'")
+
+
 def _attend_fp8(q, k, vt, kpool, seqlens, idx, cnt, nimg, text_amp, out=None):
     """The FP8 Q.K path behind the (unchanged) selection: q and k quantised per 128-token block, K after subtracting its
     mean over the sequence -- the mean of the block means the selection already has, so no further pass over K."""
@@ -82,13 +92,14 @@ def attencarve_packed(q, k, vt, top_k, seqlens, text_blocks, text_amp, prob_thre
 
 
 def _combined(query, key, value, top_k, seqlens, text_blocks, text_amp, prob_threshold, block_neighbor_list,
-              shape_xfuse, first_frame_blocks=0, context_size=None, return_mask=False, qk_dtype=None):
+              shape_xfuse, first_frame_blocks=0, context_size=None, return_mask=False, qk_dtype=None, narrow_heads="pad"):
     B, S, H, D = query.shape
     if D not in (16, 32, 64, 128):         # the Triton kernel's own assert (:155)
         raise ValueError(f"jenga_amd: head_dim must be 16, 32, 64 or 128 (got {D})")
     _check_qk_dtype(qk_dtype, D)
+    _check_narrow_heads(narrow_heads, D, qk_dtype)
     head_dim = D
-    if D != 128:
+    if D != 128 and narrow_heads == "pad":
         # Narrow heads run on the 128-channel kernels with zero channels appended: the extra products are exact zeros in
         # every dot product (pooled scores, QK^T), the extra output channels are dropped, and the two scales keep the true
         # head_dim ** -0.5.  No entry script of the reference reaches this (all three models have 128-channel heads), so
@@ -102,6 +113,18 @@ def _combined(query, key, value, top_k, seqlens, text_blocks, text_amp, prob_thr
     if nimg < 0:
         raise ValueError("text_blocks exceeds the number of blocks")
     mask = idx = cnt = None
+    if narrow_heads == "native":
+        # 64-channel rows as they lie in memory: no channel padding, no pack_v workspace, no output slice (csrc/bsattn64.hip)
+        if nimg > 0:
+            mask, idx, cnt = _capi.block_select(_capi.block_pool_d64(query, nimg), _capi.block_pool_d64(key, nb),
+                                                block_neighbor_list, nimg, text_blocks, top_k, prob_threshold,
+                                                first_frame_blocks=first_frame_blocks, want_mask=return_mask, head_dim=64)
+        out = _capi.bsattn_d64_fwd(query, key, value, seqlens, idx, cnt, nimg, 64 ** -0.5, text_amp, nimg)
+        if context_size is not None and context_size != S:
+            out = out[:, :context_size]
+        if not shape_xfuse:
+            out = out.reshape(B, out.shape[1], H * D)
+        return (out, mask) if return_mask else out
     pooled = None
     if qk_dtype == "fp8":
         pooled = (_capi.block_pool(query, nimg) if nimg > 0 else None, _capi.block_pool(key, nb))
@@ -154,11 +177,15 @@ def block_sparse_attention(
     p_remain_rates: float = 0.5,
     return_mask: bool = False,
     qk_dtype: str = None,
+    narrow_heads: str = "pad",
 ):
     """HunyuanVideo flavour.  q/k/v [B,S,H,128], S % 128 == 0 (the reference's padding branch is dead code, :331-336),
     cu_seqlens_q from get_cu_seqlens (only element [1] is used).  Returns [B,S,H*D], or [B,S,H,D] if shape_xfuse.
     qk_dtype (jenga_amd extension, also on the I2V and Wan flavours): None = 16-bit Q.K (the default); "fp8" = the same kept
-    lists, then Q and K quantised per 128-token block to e4m3fn and QK^T on the FP8 MFMA (csrc/qattn.hip), head_dim 128 only."""
+    lists, then Q and K quantised per 128-token block to e4m3fn and QK^T on the FP8 MFMA (csrc/qattn.hip), head_dim 128 only.
+    narrow_heads (jenga_amd extension, also on the I2V and Wan flavours): how heads narrower than 128 channels run.  "pad" (the
+    default): zero-padded to 128 channels on the 128-channel kernels.  "native": head_dim 64 only -- block_pool_d64,
+    block_select(head_dim=64) and bsattn_d64_fwd on the tensors as given (csrc/bsattn64.hip); same kept blocks as "pad"."""
     _check_inputs(query, key, value)
     if block_size_M != BLOCK or block_size_N != BLOCK:
         raise ValueError("jenga_amd: block sizes must be 128")
@@ -169,7 +196,7 @@ def block_sparse_attention(
     query, key, value = _unit_inner(query), _unit_inner(key), _unit_inner(value)
     seqlens = _seqlens_from_cu(cu_seqlens_q, query.device)
     return _combined(query, key, value, top_k, seqlens, text_blocks, text_amp, p_remain_rates, block_neighbor_list,
-                     shape_xfuse, return_mask=return_mask, qk_dtype=qk_dtype)
+                     shape_xfuse, return_mask=return_mask, qk_dtype=qk_dtype, narrow_heads=narrow_heads)
 
 
 def _pad_seq(t, pad):
@@ -179,7 +206,7 @@ def _pad_seq(t, pad):
 def block_sparse_attention_i2v(query, key, value, top_k, block_size_M=128, block_size_N=128, cu_seqlens_q=None,
                                cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None, text_blocks=4,
                                text_amp=0.0, block_neighbor_list=None, shape_xfuse=False, p_remain_rates=0.5,
-                               return_mask=False, qk_dtype=None):
+                               return_mask=False, qk_dtype=None, narrow_heads="pad"):
     """HunyuanVideo-I2V flavour: pads S to a multiple of 128, text_blocks defaults to 4, output sliced back."""
     _check_inputs(query, key, value)
     if cu_seqlens_q is None:
@@ -189,13 +216,14 @@ def block_sparse_attention_i2v(query, key, value, top_k, block_size_M=128, block
     q, k, v = (_pad_seq(_unit_inner(t), pad) for t in (query, key, value))
     seqlens = _seqlens_from_cu(cu_seqlens_q, query.device)
     return _combined(q, k, v, top_k, seqlens, text_blocks, text_amp, p_remain_rates, block_neighbor_list,
-                     shape_xfuse, context_size=S, return_mask=return_mask, qk_dtype=qk_dtype)
+                     shape_xfuse, context_size=S, return_mask=return_mask, qk_dtype=qk_dtype, narrow_heads=narrow_heads)
 
 
 def block_sparse_attention_wan(query, key, value, top_k, block_size_M=128, block_size_N=128, cu_seqlens_q=None,
                                cu_seqlens_kv=None, max_seqlen_q=None, max_seqlen_kv=None, text_blocks=0,
                                text_amp=0.0, block_neighbor_list=None, shape_xfuse=False, p_remain_rates=0.9,
-                               first_frame_blocks=0, return_mask=False, kv_lens=None, qk_dtype=None):
+                               first_frame_blocks=0, return_mask=False, kv_lens=None, qk_dtype=None,
+                               narrow_heads="pad"):
     """Wan flavour: always pads, computes in bf16 whatever the input dtype, seqlen = unpadded S, dense first-frame
     rule, returns the input dtype.  kv_lens (int32 [B] tensor, jenga_amd extension): keys at or beyond it are masked
     -- what WanSelfAttention's dense branch gets from flash_attention(k_lens=seq_lens) (wan/modules/model_mul.py:153-159)
@@ -212,7 +240,7 @@ def block_sparse_attention_wan(query, key, value, top_k, block_size_M=128, block
         seqlens = torch.full((B,), S, dtype=torch.int32, device=query.device)
     res = _combined(q, k, v, top_k, seqlens, text_blocks, text_amp, p_remain_rates, block_neighbor_list,
                     shape_xfuse, first_frame_blocks=first_frame_blocks, context_size=S, return_mask=return_mask,
-                    qk_dtype=qk_dtype)
+                    qk_dtype=qk_dtype, narrow_heads=narrow_heads)
     if return_mask:
         return res[0].to(out_dtype), res[1]
     return res.to(out_dtype)

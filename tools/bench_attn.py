@@ -118,13 +118,69 @@ def fp8_ab(a, q, k, vt, seqlens, idx, cnt, nimg, kpool, flops, res):
         json.dump(rec, f, indent=1)
 
 
+def d64_ab(a):
+    """--d64: 64-channel heads, the padded path against the native one on the SAME q, k, v and kept lists (the selection runs
+    once, outside the windows: it is the same work on both sides), one process, alternating windows of `--iters` calls
+    (choose it so that a window is >= 1 s), `--repeats` windows each:
+      pad_total     F.pad of q, k, v to 128 channels + pack_v + bsattn_fwd (default flags) + the slice back to 64 channels;
+      pad_attn      that bsattn_fwd alone on the padded tensors;
+      native_total = native_attn: bsattn_d64_fwd on the tensors as given (there is nothing else on that side)."""
+    import torch.nn.functional as F
+    dev = torch.device("cuda:0")
+    t, h, w = a.grid
+    S_img, tb, H = t * h * w, 2, a.heads
+    nimg, nb = S_img // 128, S_img // 128 + tb
+    S = nb * 128
+    torch.manual_seed(0)
+    q, k, v = [torch.randn(1, S, H, 64, device=dev, dtype=torch.bfloat16) for _ in range(3)]
+    nbm = G.gilbert_block_neighbor_mapping(t, h, w, as_tensor=True)
+    top_k = int((1 - a.drop) * nimg)
+    seqlens = torch.tensor([S_img + a.valid_text], dtype=torch.int32, device=dev)
+    _, idx, cnt = _capi.block_select(_capi.block_pool_d64(q, nimg), _capi.block_pool_d64(k, nb), nbm, nimg, tb, top_k, a.p,
+                                     head_dim=64)
+    sm = 64 ** -0.5
+    pad = lambda x: F.pad(x, [0, 64])
+    qp, kp, vtp = pad(q), pad(k), _capi.pack_v(pad(v), nb)
+    paths = {"pad_total": lambda: _capi.bsattn_fwd(pad(q), pad(k), _capi.pack_v(pad(v), nb), seqlens, idx, cnt, nimg, sm, 0.0,
+                                                   nimg)[..., :64].contiguous(),
+             "pad_attn": lambda: _capi.bsattn_fwd(qp, kp, vtp, seqlens, idx, cnt, nimg, sm, 0.0, nimg),
+             "native_attn": lambda: _capi.bsattn_d64_fwd(q, k, v, seqlens, idx, cnt, nimg, sm, 0.0, nimg)}
+    o_pad, o_nat = paths["pad_total"]().float(), paths["native_attn"]().float()      # warm-up; the difference at the timed size
+    paths["pad_attn"]()
+    torch.cuda.synchronize()
+    d = o_nat - o_pad
+    pairs = int(cnt.sum().item()) + H * tb * nb
+    flops = 4 * 128 * 128 * 64 * pairs
+    rec = {"shape": dict(S=S, H=H, D=64, nb=nb, top_k=top_k, p=a.p, drop=a.drop), "pairs": pairs, "flop": flops,
+           "default_flags": _capi.ATTN_DEFAULT_FLAGS, "iters_per_window": a.iters, "repeats": a.repeats,
+           "finite": bool(torch.isfinite(o_nat).all().item()),
+           "native_vs_pad": {"max_abs": float(d.abs().max().item()), "rms": float(d.pow(2).mean().sqrt().item()),
+                             "rms_of_output": float(o_pad.pow(2).mean().sqrt().item())}}
+    del o_pad, o_nat, d
+    ms = {n: [] for n in paths}
+    for _ in range(a.repeats):
+        for n, f in paths.items():                     # alternate inside every repeat
+            ms[n].append(timed(f, a.iters, warmup=0)[0])
+    for n, xs in ms.items():
+        med = sorted(xs)[len(xs) // 2]
+        rec[n] = {"ms_per_call": xs, "median_ms": med, "spread_ms": max(xs) - min(xs), "TFLOPs": flops / (med * 1e-3) / 1e12}
+    rec["speedup_native_over_pad_total"] = rec["pad_total"]["median_ms"] / rec["native_attn"]["median_ms"]
+    rec["speedup_native_over_pad_attn"] = rec["pad_attn"]["median_ms"] / rec["native_attn"]["median_ms"]
+    print(json.dumps(rec), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.d64_out)), exist_ok=True)
+    with open(a.d64_out, "w") as f:
+        json.dump(rec, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--d64", action="store_true", help="A/B at 64-channel heads: zero-padded 128-channel path vs bsattn_d64_fwd")
+    ap.add_argument("--d64-out", default="profiles/bsattn_d64_ab.json", help="--d64: where the record goes")
     ap.add_argument("--fp8", action="store_true", help="A/B of the attention launch: 16-bit default vs the FP8 Q.K kernel")
     ap.add_argument("--fp8-out", default="profiles/bsattn_fp8_ab.json", help="--fp8: where the record goes")
     ap.add_argument("--dense", action="store_true", help="A/B of the dense call: lists path vs the dense varlen kernel")
     ap.add_argument("--dense-shapes", nargs="*", default=[], help="--dense: subset of " + ", ".join(DENSE_SHAPES))
-    ap.add_argument("--repeats", type=int, default=3, help="--dense / --fp8: timed windows per path")
+    ap.add_argument("--repeats", type=int, default=3, help="--dense / --fp8 / --d64: timed windows per path")
     ap.add_argument("--out", default="profiles/dense_varlen_ab.json", help="--dense: where the record goes")
     ap.add_argument("--heads", type=int, default=24)
     ap.add_argument("--grid", type=int, nargs=3, default=[32, 45, 80])
@@ -160,6 +216,8 @@ def main():
     a = ap.parse_args()
     if a.dense:
         return dense_ab(a)
+    if a.d64:
+        return d64_ab(a)
     dev = torch.device("cuda:0")
     t, h, w = a.grid
     S_img, tb = t * h * w, 2
