@@ -404,6 +404,36 @@ int jenga_bsattn_fp8_fwd(void* stream, const void* q8, const float* q_scale, con
                          float text_amp, int64_t text_block_start, int dtype, int flags);
 
 /* ---------------------------------------------------------------------------------------------------
+ * FP8 linear layers (csrc/gemm8.hip; additive exports inside ABI 4).  An opt-in variant of the dense layers behind jenga_linear
+ * (same reference lines: models_mul_block_gc_ha_multigpu.py:404-406, 498-499 for the GELU form, :297-315, 500 and
+ * modulate_layers.py:53-68 for the gate / residual form) whose product runs on e4m3fn operands with v_mfma_f32_32x32x64_f8f6f4 in a
+ * hand-written kernel: twice the bf16 MFMA rate, half the operand bytes through HBM, L2 and LDS.  No hipBLASLt, no workspace, no
+ * split-K, no state besides the per-kernel "dynamic LDS size set" flag.
+ *
+ * jenga_quant_fp8_rows: x [rows, K] (dtype, row stride in elements, a multiple of 8; K a multiple of 16) -> x8 uint8 [rows, K]
+ *   (OCP e4m3fn bytes, row stride in bytes, a multiple of 16) and scale fp32 [rows].  Per ROW, in IEEE fp32:
+ *       amax = max_k |float(x[r,k])|;   s = fmaxf(amax, 1e-30f) / 448.0f;   x8 = e4m3fn_rne(float(x) / s)  (a true division);
+ *       scale[r] = s.
+ *   The recipe of jenga_quant_fp8_blocks with one scale per row.  Serves activations (one scale per token) and weights
+ *   (w [N, K]: one scale per output channel).  x and x8 16-byte aligned; anything else: JENGA_EINVAL.
+ * jenga_linear_fp8:
+ *       out[m, n] = act( gate[n] * ( x_scale[m] * w_scale[n] * sum_k x8[m,k] w8[n,k] )  +  bias[n]  +  res[m, n] )
+ *   x8 [M,K], w8 [N,K] e4m3fn bytes with their row scales (fp32 [M], [N]); the products are exact in the fp32 accumulator,
+ *   the two scales are applied to it as acc * (x_scale[m] * w_scale[n]) before gate, bias and residual; ONE rounding to dtype.
+ *   bias, gate, res, act (JENGA_ACT_GELU_TANH, JENGA_BIAS_F32, JENGA_OUT_F32) and dtype mean what they mean for the 16-bit
+ *   entry above, and the combinations refused there are refused here (JENGA_EUNSUPPORTED).
+ *   JENGA_EINVAL unless: M, N, K >= 1; K a multiple of 128; N a multiple of 8; row strides of x8 / w8 multiples of 16 bytes in
+ *   [K, 2^24]; row strides of res / out multiples of 8 elements >= N; x8, w8, w_scale, bias, gate, res, out 16-byte aligned.
+ *   M and N need not be multiples of the 256 x 256 tile: nothing outside [0,M) x [0,K) and [0,N) x [0,K) is read, nothing outside
+ *   [0,M) x [0,N) is written.  Deterministic.  Close to, not bit-equal with, the 16-bit entry (8-bit x and w). */
+int jenga_quant_fp8_rows(void* stream, const void* x, void* x8, float* scale, int64_t rows, int64_t K,
+                         int64_t x_row_stride, int64_t x8_row_stride, int dtype);
+int jenga_linear_fp8(void* stream, const void* x8, const float* x_scale, const void* w8, const float* w_scale,
+                     const void* bias, const void* res, const float* gate, void* out, int64_t M, int64_t N, int64_t K,
+                     int64_t x_row_stride, int64_t w_row_stride, int64_t res_row_stride, int64_t out_row_stride,
+                     int act, int dtype);
+
+/* ---------------------------------------------------------------------------------------------------
  * Block-sparse attention on 64-channel heads (csrc/bsattn64.hip; additive exports inside ABI 4).  The reference's Triton kernel
  * accepts head dim 64 (attention_block_triton_diffres.py:155); these two entries run it without zero-padding the rows to 128
  * channels, without a jenga_pack_v workspace and without slicing the output.

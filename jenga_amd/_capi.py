@@ -63,6 +63,8 @@ SIGNATURES = {
     "jenga_dense_varlen_fwd": (_i32, [_vp] * 7 + [_i64] * 12 + [_f32, _i32]),
     "jenga_quant_fp8_blocks": (_i32, [_vp] * 5 + [_i64] * 6 + [_i32]),
     "jenga_bsattn_fp8_fwd": (_i32, [_vp] * 10 + [_i64] * 13 + [_f32, _f32, _i64, _i32, _i32]),
+    "jenga_quant_fp8_rows": (_i32, [_vp] * 4 + [_i64] * 4 + [_i32]),
+    "jenga_linear_fp8": (_i32, [_vp] * 9 + [_i64] * 7 + [_i32, _i32]),
     "jenga_block_pool_d64": (_i32, [_vp, _vp, _vp] + [_i64] * 6 + [_i32]),
     "jenga_bsattn_d64_fwd": (_i32, [_vp] * 8 + [_i64] * 16 + [_f32, _f32, _i64, _i32, _i32]),
     "jenga_linear_export_choices": (_i64, [_vp, _i64]),
@@ -504,8 +506,8 @@ def gelu_tanh(x, out=None):
 
 
 ACT_NONE, ACT_GELU_TANH = 0, 1
-BIAS_F32 = 256
-OUT_F32 = 512      # OR-ed into jenga_linear's `act`: the bias vector is float32
+BIAS_F32 = 256     # OR-ed into jenga_linear's `act`: the bias vector is float32
+OUT_F32 = 512      # OR-ed into jenga_linear's `act`: res and out are float32
 _GEMM_WORKSPACE = __import__("collections").OrderedDict()
 _GEMM_WORKSPACE_MAX = 8         # scratch buffers kept per process (64 MiB each), least recently used evicted
 
@@ -594,6 +596,77 @@ def linear(x, weight, bias=None, act=ACT_NONE, gate=None, res=None, out=None):
         _check(lib().jenga_linear(_stream(x.device), _p(x2), _p(weight), _p(bias), _p(r2), _p(g32), _p(o2), M, N, K, xrs,
                                   weight.stride(0), rrs, ors, int(act), _p(ws), ws.numel(), dtype_code(x.dtype)),
                "jenga_linear")
+    return out
+
+
+def quant_fp8_rows(x, out=None):
+    """x [..., K] (bf16 / fp16, uniform row stride, K a multiple of 16) -> (x8 uint8 [..., K] of e4m3fn bytes, scale fp32
+    [rows]): per row s = max(amax |x|, 1e-30) / 448, x8 = e4m3fn(x / s) (csrc/gemm8.hip).  out: a uint8 [..., K] destination
+    (may be a row-strided view).  Serves activations (a scale per token) and weights [N, K] (a scale per output channel)."""
+    x2, rows, K, xrs = _rows2d(x)
+    if rows < 1 or K % 16 or xrs % 8:
+        raise ValueError("quant_fp8_rows: x must have at least one row, K a multiple of 16 and a row stride multiple of 8")
+    _need_gpu(x, "quant_fp8_rows")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    o2, ro, Ko, ors = _rows2d(out)
+    if out.dtype != torch.uint8 or ro != rows or Ko != K or ors % 16 or out.device != x.device:
+        raise ValueError("quant_fp8_rows: out must be uint8 [..., K] on x's device with a row stride multiple of 16")
+    scale = torch.empty(rows, dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        _check(lib().jenga_quant_fp8_rows(_stream(x.device), _p(x2), _p(o2), _p(scale), rows, K, xrs, ors,
+                                          dtype_code(x.dtype)), "jenga_quant_fp8_rows")
+    return out, scale
+
+
+def linear_fp8(x8, x_scale, w8, w_scale, bias=None, act=ACT_NONE, gate=None, res=None, out=None, dtype=torch.bfloat16):
+    """linear() on e4m3fn operands (jenga_linear_fp8, csrc/gemm8.hip): out = act(gate * (x_scale[m] * w_scale[n] * (x8 @ w8.T))
+    + bias + res).  x8 uint8 [..., K] and x_scale fp32 [rows], w8 uint8 [N, K] and w_scale fp32 [N] from quant_fp8_rows; K a
+    multiple of 128, N of 8.  bias / gate / res / out as for linear(): a float32 bias is passed on as float32, a float32 res or
+    out selects the fp32 form, res / out may be strided views.  dtype: the 16-bit type of bias, res and out."""
+    x2, M, K, xrs = _rows2d(x8)
+    if x8.dtype != torch.uint8 or w8.dtype != torch.uint8 or w8.dim() != 2 or w8.shape[1] != K or w8.stride(1) != 1:
+        raise ValueError("linear_fp8: x8 must be uint8 [..., K] and w8 uint8 [N, K] with contiguous rows")
+    N = w8.shape[0]
+    if M < 1 or K % 128 or N % 8 or xrs % 16 or w8.stride(0) % 16:
+        raise ValueError("linear_fp8: M >= 1, K a multiple of 128, N a multiple of 8, row strides of x8 / w8 multiples of 16")
+    for s_, n_, what in ((x_scale, M, "x_scale"), (w_scale, N, "w_scale")):
+        if s_.dtype != torch.float32 or s_.dim() != 1 or s_.numel() != n_ or not s_.is_contiguous() or s_.device != x8.device:
+            raise ValueError(f"linear_fp8: {what} must be a contiguous float32 vector with one entry per row")
+    code = dtype_code(dtype)
+    out32 = (res is not None and res.dtype == torch.float32) or (out is not None and out.dtype == torch.float32)
+    odt = torch.float32 if out32 else dtype
+    if int(act) & 0xff and (out32 or gate is not None or res is not None):
+        raise ValueError("linear_fp8: the activation epilogue cannot be combined with gate / residual / float32 output")
+    _need_gpu(x8, "linear_fp8")
+    _need_gpu(w8, "linear_fp8")
+    if out is None:
+        out = torch.empty(tuple(x8.shape[:-1]) + (N,), dtype=odt, device=x8.device)
+    o2, Mo, No, ors = _rows2d(out)
+    if Mo != M or No != N or out.dtype != odt or ors % 8:
+        raise ValueError("linear_fp8: out must be [..., N] in dtype (float32 when the residual is) with as many rows as x8")
+    r2, rrs = None, 0
+    if res is not None:
+        r2, Mr, Nr, rrs = _rows2d(res)
+        if Mr != M or Nr != N or res.dtype != odt or rrs % 8:
+            raise ValueError("linear_fp8: res must match out")
+    act = int(act) | (OUT_F32 if out32 else 0)
+    if bias is not None:
+        if bias.dtype == torch.float32:
+            act |= BIAS_F32
+            bias = bias.reshape(-1).contiguous()
+        else:
+            bias = bias.reshape(-1).to(dtype=dtype).contiguous()
+        if bias.numel() != N:
+            raise ValueError("linear_fp8: bias must have N entries")
+    g32 = None
+    if gate is not None:
+        g32 = gate.reshape(-1).to(dtype=torch.float32).contiguous()
+        if g32.numel() != N:
+            raise ValueError("linear_fp8: gate must have N entries")
+    with _on(x8.device):
+        _check(lib().jenga_linear_fp8(_stream(x8.device), _p(x2), _p(x_scale), _p(w8), _p(w_scale), _p(bias), _p(r2), _p(g32),
+                                      _p(o2), M, N, K, xrs, w8.stride(0), rrs, ors, act, code), "jenga_linear_fp8")
     return out
 
 

@@ -46,6 +46,8 @@ SOURCES = [
     ("qattn.hip", ["-fno-honor-nans", "-Wno-inline-asm"] + NO_PK),
     # the 64-channel block-sparse kernel and its pooling: same flags (the softmax's scalar adds and multiplies are written out)
     ("bsattn64.hip", ["-fno-honor-nans", "-Wno-inline-asm"] + NO_PK),
+    # the FP8 GEMM and its per-row quantiser: qattn.hip's flags (the epilogue's scalar fp32 is written out, no packed fp32)
+    ("gemm8.hip", ["-fno-honor-nans", "-Wno-inline-asm"] + NO_PK),
 ]
 
 def _hipcc():

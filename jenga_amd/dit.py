@@ -68,6 +68,30 @@ class ModulateDiT(nn.Module):
         return self.linear(self.act(x))
 
 
+# JENGA_LINEAR_DTYPE=fp8 (opt-in): the two fused GEMM sites below (MLP.hidden, linear_gate_residual without a mask) run as
+# quant_fp8_rows(x) + linear_fp8 (csrc/gemm8.hip: per-token / per-output-channel e4m3fn, a hand-written FP8 GEMM with the
+# same epilogues).  "bf16", the default, is the hipBLASLt path, untouched.  Record: DESIGN.md section 3.11.
+LINEAR_DTYPE = os.environ.get("JENGA_LINEAR_DTYPE", "bf16")
+if LINEAR_DTYPE not in ("bf16", "fp8"):
+    raise ValueError(f"JENGA_LINEAR_DTYPE must be 'bf16' or 'fp8', got {LINEAR_DTYPE!r}")
+
+
+def _fp8_weight(lin):
+    """(w8, w_scale) of an nn.Linear, quantised once and kept on the module until its weight is replaced or written."""
+    w = lin.weight
+    key = (w.data_ptr(), w._version)
+    hit = getattr(lin, "_jenga_fp8", None)
+    if hit is None or hit[0] != key:
+        hit = lin._jenga_fp8 = (key,) + tuple(_capi.quant_fp8_rows(w.detach()))
+    return hit[1], hit[2]
+
+
+def _linear_fp8(lin, x, bias, **epilogue):
+    x8, xs = _capi.quant_fp8_rows(x)
+    w8, ws = _fp8_weight(lin)
+    return _capi.linear_fp8(x8, xs, w8, ws, bias, dtype=x.dtype, **epilogue)
+
+
 class MLP(nn.Module):
     def __init__(self, in_channels, hidden_channels, dtype=None, device=None):
         super().__init__()
@@ -77,6 +101,8 @@ class MLP(nn.Module):
     def hidden(self, x):
         # fc1 + bias + tanh-GELU in ONE hipBLASLt call (jenga_linear: GELU epilogue on the fp32 accumulator): the separate
         # activation pass was 5.7 GB of HBM traffic per layer at the 720p shape
+        if LINEAR_DTYPE == "fp8":
+            return _linear_fp8(self.fc1, x, self.fc1.bias, act=_capi.ACT_GELU_TANH)
         return _capi.linear(x, self.fc1.weight, self.fc1.bias, act=_capi.ACT_GELU_TANH)
 
     def forward(self, x):
@@ -147,6 +173,8 @@ def linear_gate_residual(lin, x, gate, res, gate2=None, mask=None):
         # gate * bias in fp32, handed to the GEMM as a float32 bias vector (JENGA_BIAS_F32): no extra rounding on its way
         # into the fp32 accumulator.  JENGA_GATED_BIAS=bf16 restores round 3's bf16 product (one more rounding)
         bias = lin.bias.float() * g.float() if GATED_BIAS_F32 else lin.bias * g.to(lin.bias.dtype)
+    if LINEAR_DTYPE == "fp8":
+        return _linear_fp8(lin, x, bias, gate=g, res=res)
     return _capi.linear(x, lin.weight, bias, gate=g, res=res)
 
 
