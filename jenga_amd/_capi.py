@@ -1,6 +1,7 @@
 """ctypes binding of libjenga_amd.so (include/jenga_amd.h).  No compute happens in Python: every function
 enqueues HIP kernels on torch's current stream and raises if the library is missing or a call fails.
 There is NO CPU fallback on purpose: the product path must fail loudly when the HIP extension is absent."""
+import collections
 import ctypes
 import os
 
@@ -10,14 +11,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JENGA_LIB", os.path.join(_HERE, "libjenga_amd.so"))
 
 JENGA_BF16, JENGA_FP16 = 0, 1
-# jenga_bsattn_fwd flags (include/jenga_amd.h).  No kernel bit = the round-1 kernel, exactly as in the C header.
-ATTN_XCD_REMAP = 1
+# jenga_bsattn_fwd flags.  XCD_REMAP, BALANCE and LP are the header's (include/jenga_amd.h); SORTED and PAIR are resolved here.
+ATTN_XCD_REMAP = 1   # contiguous ranges of query blocks per XCD (L2 locality); without it: plain head-major order
 ATTN_BALANCE = 4     # query blocks (pairs) DRAWN from per-XCD queues on an oversubscribed grid: evens out the speed differences
-#                      between the XCDs of a chip; bit-identical; in the default since round 4
-ATTN_LEGACY = 0      # (readability alias) no kernel bit: the round-1 kernel, one query block per 4-wave workgroup
-ATTN_LP = 8          # round-1 decomposition + in-wave software pipeline (csrc/bsattn3.hip)
+#                      between the XCDs of a chip; bit-identical to the static mapping
+ATTN_LEGACY = 0      # (readability alias) no kernel bit: the plain kernel, one query block per 4-wave workgroup (csrc/bsattn.hip)
+ATTN_LP = 8          # the same decomposition with an in-wave software pipeline (csrc/bsattn3.hip)
 ATTN_SORTED = 16     # (Python-side) kept-count-aware launch order: jenga_order_by_count feeds jenga_bsattn_fwd's `order`
-ATTN_PAIR = 64       # (Python-side) route to jenga_pair_merge + jenga_bsattn_pair_fwd: the pair kernel of round 5
+ATTN_PAIR = 64       # (Python-side) route to jenga_pair_merge + jenga_bsattn_pair_fwd: the pair kernel
 #                      (csrc/bsattn5.hip: two Hilbert-adjacent query blocks per workgroup, 64 query rows per wave)
 # LP default: LP kernel, XCD remap, kept-count-aware order inside every XCD's range (+3.3 % sustained on lists whose counts
 # vary: profiles/r03_attn_order_ab.json), cross-XCD balancing (-1.7 % loop time: profiles/r04_attn_balance_ab.json).
@@ -75,6 +76,7 @@ SIGNATURES = {
 }
 
 _lib = None
+_bound = {}     # name -> the library's function, filled by lib(): the launch helpers look a name up once, here
 
 
 class AttnProfile:
@@ -116,6 +118,26 @@ class AttnProfile:
 ATTN_PROFILE = None
 
 
+def _profile_start():
+    """-> the start event of one attention launch, recorded on the current stream (inside the launch's device guard)"""
+    e0 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return e0
+
+
+def _profile_stop(prof, e0, B, H, n_blocks, nq_img, idx, cnt):
+    """the stop event of that launch, and its kept (q-block, kv-block) pairs: the lists' counts + every pair of the text rows"""
+    e1 = torch.cuda.Event(enable_timing=True)
+    e1.record()
+    prof.events.append((e0, e1))
+    prof.launches += 1
+    tot = (cnt.sum(dtype=torch.int64) if cnt is not None else 0) + B * H * (n_blocks - nq_img) * n_blocks
+    prof.pairs = tot if prof.pairs is None else prof.pairs + tot
+    prof.per_launch.append((prof.tag, tot))
+    if idx is not None and nq_img > 1:
+        prof.last_lists = (idx, cnt)
+
+
 class JengaError(RuntimeError):
     pass
 
@@ -129,12 +151,14 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -m jenga_amd.build` (hipcc --offload-arch=gfx950). "
                 "jenga_amd has no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH)
+        bound = {}
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
+            fn = bound[name] = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         if L.jenga_abi_version() != 4:
             raise JengaError("libjenga_amd.so ABI version mismatch; rebuild")
         _lib = L
+        _bound.update(bound)
     return _lib
 
 
@@ -158,7 +182,7 @@ class _Here:
 
 
 _HERE_CTX = _Here()
-_ALWAYS_GUARD = os.environ.get("JENGA_DEVICE_GUARD", "") == "always"     # (A/B switch: round 3's behaviour)
+_ALWAYS_GUARD = os.environ.get("JENGA_DEVICE_GUARD", "") == "always"     # (A/B switch: torch's device guard around every launch)
 
 
 def _on(device):
@@ -194,15 +218,123 @@ def _bshd_strides(t):
     return t.stride(0), t.stride(1), t.stride(2)
 
 
+def _enqueue(name, device, *args):
+    """The library's `name` on torch's current stream of `device`, which the caller has made current (_on)."""
+    rc = (_bound.get(name) or getattr(lib(), name))(_stream(device), *args)
+    if rc:
+        _check(rc, name)
+
+
+def _launch(name, device, *args):
+    """_enqueue under the device guard.  Written out, not a call of it: this is the host path of every launch, and a Python
+    frame is a measurable share of it (tools/host_overhead.py)."""
+    fn = _bound.get(name) or getattr(lib(), name)
+    with _on(device):
+        rc = fn(_stream(device), *args)
+    if rc:
+        _check(rc, name)
+
+
+# ------------------------------------------------------------------------------------------------ shared argument checks
+def _flat(t, dtype):
+    """A per-channel vector ([C], [1,C], ...) or None -> contiguous [C] in `dtype`."""
+    return None if t is None else t.reshape(-1).to(dtype=dtype).contiguous()
+
+
+def _norm_weight(w, like):
+    """RMSNorm weight or None -> contiguous, on the device and in the dtype of the tensor it scales."""
+    return None if w is None else w.to(device=like.device, dtype=like.dtype).contiguous()
+
+
+def _rope_tables(cos, sin, s_rope, S):
+    """cos / sin fp32 [>= s_rope, 128] -> (cos, sin, s_rope) with contiguous tables; s_rope defaults to the tables' length and
+    may exceed neither them nor the sequence.  No tables: s_rope = 0."""
+    if cos is None:
+        return cos, sin, 0
+    if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape[-1] != 128:
+        raise ValueError("cos/sin must be float32 [S,128]")
+    if s_rope is None:
+        s_rope = cos.shape[0]
+    if s_rope > cos.shape[0] or s_rope > S:
+        raise ValueError("s_rope exceeds the table / sequence length")
+    return cos.contiguous(), sin.contiguous(), s_rope
+
+
+def _pool_blocks(pool, name, B, H, dtype):
+    """A block-mean output [B,H,n,128] of qk_norm_rope_pool -> n (0: no such output)."""
+    if pool is None:
+        return 0
+    if pool.dim() != 4 or pool.shape[0] != B or pool.shape[1] != H or pool.shape[3] != 128 or not pool.is_contiguous() \
+            or pool.dtype != dtype:
+        raise ValueError(f"{name} must be a contiguous [B,H,n,128] tensor of the input dtype")
+    return pool.shape[2]
+
+
+def _attn_lists(what, device, B, H, n_blocks, nq_img, seqlens, idx, cnt):
+    """The list arguments of the block-sparse attention entries -> seqlens as int32 on `device`.  seqlens: at least B entries;
+    0 <= nq_img <= n_blocks; with image query blocks, idx / cnt contiguous int32 [B,H,nq_img,n_blocks] / [B,H,nq_img] there."""
+    if seqlens is not None and (seqlens.dtype != torch.int32 or seqlens.device != device):
+        seqlens = seqlens.to(device=device, dtype=torch.int32)
+    if seqlens is not None and seqlens.numel() < B:
+        # the reference passes cu_seqlens_q[1:2] whatever the batch (attention_block_triton_diffres.py:327-329) and its
+        # kernel then reads past it for B > 1; here that is an error instead of an out-of-bounds read
+        raise ValueError(f"{what}: seqlens has {seqlens.numel()} entries for batch {B}")
+    if not 0 <= nq_img <= n_blocks:
+        raise ValueError(f"{what}: nq_img must lie in [0, n_blocks]")
+    if nq_img > 0 and (idx is None or cnt is None or tuple(idx.shape) != (B, H, nq_img, n_blocks)
+                       or tuple(cnt.shape) != (B, H, nq_img) or idx.dtype != torch.int32 or cnt.dtype != torch.int32
+                       or not idx.is_contiguous() or not cnt.is_contiguous() or idx.device != device
+                       or cnt.device != device):
+        raise ValueError(f"{what}: idx / cnt must be contiguous int32 [B,H,nq_img,n_blocks] / [B,H,nq_img] on the device")
+    return seqlens
+
+
+def _out_f32(res, out):
+    """a float32 residual (or out) selects the fp32 C / D form of the GEMMs (the Wan blocks' residual stream)"""
+    return (res is not None and res.dtype == torch.float32) or (out is not None and out.dtype == torch.float32)
+
+
+def _gemm_epilogue(what, x, M, N, dtype, bias, act, gate, res, out, stride_multiple=1):
+    """The epilogue operands linear and linear_fp8 share -> (bias, gate32, res2d, res_row_stride, out, out2d, out_row_stride,
+    act).  A float32 res or out selects the fp32 C / D form (OUT_F32 in `act`; res and out then both float32), otherwise both
+    are `dtype`; out is allocated beside x if not given; a float32 bias stays float32 (BIAS_F32 in `act`), any other is cast to
+    `dtype`; gate becomes fp32 [N].  stride_multiple: what the row strides of res and out must be a multiple of (the FP8
+    kernel's vector stores: 8).  Which activations go with which operands is the caller's rule."""
+    out32 = _out_f32(res, out)
+    odt = torch.float32 if out32 else dtype
+    if out is None:
+        out = torch.empty(tuple(x.shape[:-1]) + (N,), dtype=odt, device=x.device)
+    o2, Mo, No, ors = _rows2d(out)
+    if Mo != M or No != N or out.dtype != odt or ors % stride_multiple:
+        raise ValueError(f"{what}: out must be [..., N] with as many rows as the input, float32 when the residual is float32"
+                         + (f", row stride a multiple of {stride_multiple}" if stride_multiple > 1 else ""))
+    r2, rrs = None, 0
+    if res is not None:
+        r2, Mr, Nr, rrs = _rows2d(res)
+        if Mr != M or Nr != N or res.dtype != odt or rrs % stride_multiple:
+            raise ValueError(f"{what}: res must match out")
+    act = int(act) | (OUT_F32 if out32 else 0)
+    if bias is not None:
+        bias32 = bias.dtype == torch.float32     # (the gated bias of proj / fc2 / linear2: kept unrounded)
+        act |= BIAS_F32 if bias32 else 0
+        bias = bias.reshape(-1).contiguous() if bias32 else bias.reshape(-1).to(dtype=dtype).contiguous()
+        if bias.numel() != N:
+            raise ValueError(f"{what}: bias must have N entries")
+    g32 = None
+    if gate is not None:
+        g32 = gate.reshape(-1).to(dtype=torch.float32).contiguous()
+        if g32.numel() != N:
+            raise ValueError(f"{what}: gate must have N entries")
+    return bias, g32, r2, rrs, out, o2, ors, act
+
+
 # ------------------------------------------------------------------------------------------------ geometry
 def gilbert_map(t, h, w, sliced, device):
     n = t * h * w
     l2h = torch.empty(n, dtype=torch.int64, device=device)
     h2l = torch.empty(n, dtype=torch.int64, device=device)
     _need_gpu(l2h, "gilbert_map")
-    with _on(l2h.device):
-        _check(lib().jenga_gilbert_map(_stream(l2h.device), t, h, w, int(bool(sliced)), _p(l2h), _p(h2l)),
-               "jenga_gilbert_map")
+    _launch("jenga_gilbert_map", l2h.device, t, h, w, int(bool(sliced)), _p(l2h), _p(h2l))
     return l2h, h2l
 
 
@@ -211,9 +343,7 @@ def gilbert_neighbors(t, h, w, block, l2h):
     n = t * h * w
     nb = (n + block - 1) // block
     out = torch.zeros((nb, nb), dtype=torch.uint8, device=l2h.device)
-    with _on(l2h.device):
-        _check(lib().jenga_gilbert_neighbors(_stream(l2h.device), t, h, w, block, _p(l2h), _p(out)),
-               "jenga_gilbert_neighbors")
+    _launch("jenga_gilbert_neighbors", l2h.device, t, h, w, block, _p(l2h), _p(out))
     return out.view(torch.bool)
 
 
@@ -230,9 +360,7 @@ def gather_rows(src, index, out=None):
     if out is None:
         out = torch.empty((B, M, C), dtype=src.dtype, device=src.device)
     rb = C * src.element_size()
-    with _on(src.device):
-        _check(lib().jenga_gather_rows(_stream(src.device), _p(src), _p(out), _p(index), B, M, rb, N * rb, M * rb),
-               "jenga_gather_rows")
+    _launch("jenga_gather_rows", src.device, _p(src), _p(out), _p(index), B, M, rb, N * rb, M * rb)
     return out
 
 
@@ -245,21 +373,10 @@ def rmsnorm_rope(x, weight, cos, sin, s_rope=None, eps=1e-6, out=None):
     if out is None:
         out = torch.empty((B, S, H, 128), dtype=x.dtype, device=x.device)
     xs, os_ = _bshd_strides(x), _bshd_strides(out)
-    if weight is not None:
-        weight = weight.to(device=x.device, dtype=x.dtype).contiguous()
-    if cos is not None:
-        if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape[-1] != 128:
-            raise ValueError("cos/sin must be float32 [S,128]")
-        cos, sin = cos.contiguous(), sin.contiguous()
-        if s_rope is None:
-            s_rope = cos.shape[0]
-        if s_rope > cos.shape[0] or s_rope > S:
-            raise ValueError("s_rope exceeds the table / sequence length")
-    else:
-        s_rope = 0
-    with _on(x.device):
-        _check(lib().jenga_rmsnorm_rope(_stream(x.device), _p(x), _p(out), _p(weight), _p(cos), _p(sin), B, S, H,
-                                        *xs, *os_, s_rope, float(eps), dtype_code(x.dtype)), "jenga_rmsnorm_rope")
+    weight = _norm_weight(weight, x)
+    cos, sin, s_rope = _rope_tables(cos, sin, s_rope, S)
+    _launch("jenga_rmsnorm_rope", x.device, _p(x), _p(out), _p(weight), _p(cos), _p(sin), B, S, H, *xs, *os_, s_rope,
+            float(eps), dtype_code(x.dtype))
     return out
 
 
@@ -277,34 +394,13 @@ def qk_norm_rope_pool(xq, xk, wq, wk, cos, sin, out_q, out_k, s_rope=None, qpool
         raise ValueError("qk_norm_rope_pool: q and k (and their outputs) must share their strides")
     if H > 64:
         raise ValueError("qk_norm_rope_pool: at most 64 heads")
-    wq = None if wq is None else wq.to(device=xq.device, dtype=xq.dtype).contiguous()
-    wk = None if wk is None else wk.to(device=xq.device, dtype=xq.dtype).contiguous()
-    if cos is not None:
-        if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape[-1] != 128:
-            raise ValueError("cos/sin must be float32 [S,128]")
-        cos, sin = cos.contiguous(), sin.contiguous()
-        if s_rope is None:
-            s_rope = cos.shape[0]
-        if s_rope > cos.shape[0] or s_rope > S:
-            raise ValueError("s_rope exceeds the table / sequence length")
-    else:
-        s_rope = 0
-    nq = nk = 0
-    if qpool is not None:
-        if qpool.dim() != 4 or qpool.shape[0] != B or qpool.shape[1] != H or qpool.shape[3] != 128 \
-                or not qpool.is_contiguous() or qpool.dtype != xq.dtype:
-            raise ValueError("qpool must be a contiguous [B,H,nq,128] tensor of the input dtype")
-        nq = qpool.shape[2]
-    if kpool is not None:
-        if kpool.dim() != 4 or kpool.shape[0] != B or kpool.shape[1] != H or kpool.shape[3] != 128 \
-                or not kpool.is_contiguous() or kpool.dtype != xq.dtype:
-            raise ValueError("kpool must be a contiguous [B,H,nk,128] tensor of the input dtype")
-        nk = kpool.shape[2]
-    with _on(xq.device):
-        _check(lib().jenga_qk_norm_rope_pool(_stream(xq.device), _p(xq), _p(xk), _p(out_q), _p(out_k), _p(wq), _p(wk),
-                                             _p(cos), _p(sin), _p(qpool), _p(kpool), B, S // 128, H,
-                                             *_bshd_strides(xq), *_bshd_strides(out_q), int(s_rope), int(pool_block0),
-                                             nq, nk, float(eps), dtype_code(xq.dtype)), "jenga_qk_norm_rope_pool")
+    wq, wk = _norm_weight(wq, xq), _norm_weight(wk, xq)
+    cos, sin, s_rope = _rope_tables(cos, sin, s_rope, S)
+    nq = _pool_blocks(qpool, "qpool", B, H, xq.dtype)
+    nk = _pool_blocks(kpool, "kpool", B, H, xq.dtype)
+    _launch("jenga_qk_norm_rope_pool", xq.device, _p(xq), _p(xk), _p(out_q), _p(out_k), _p(wq), _p(wk), _p(cos), _p(sin),
+            _p(qpool), _p(kpool), B, S // 128, H, *_bshd_strides(xq), *_bshd_strides(out_q), int(s_rope), int(pool_block0),
+            nq, nk, float(eps), dtype_code(xq.dtype))
     return out_q, out_k
 
 
@@ -351,23 +447,11 @@ def sp_qkv_prologue(xq, xk, xv, wq, wk, cos, sin, out_q, out_k, out_v, heads_per
     for t in outs:
         if t.shape != o0.shape or t.stride() != o0.stride() or t.dtype != x0.dtype:
             raise ValueError("sp_qkv_prologue: the outputs must share shape, strides and dtype")
-    wq = None if wq is None else wq.to(device=x0.device, dtype=x0.dtype).contiguous()
-    wk = None if wk is None else wk.to(device=x0.device, dtype=x0.dtype).contiguous()
-    if cos is not None:
-        if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape[-1] != 128:
-            raise ValueError("cos/sin must be float32 [S,128]")
-        cos, sin = cos.contiguous(), sin.contiguous()
-        if s_rope is None:
-            s_rope = cos.shape[0]
-        if s_rope > cos.shape[0] or s_rope > S:
-            raise ValueError("s_rope exceeds the table / sequence length")
-    else:
-        s_rope = 0
-    with _on(x0.device):
-        _check(lib().jenga_sp_qkv_prologue(_stream(x0.device), _p(xq), _p(xk), _p(xv), _p(out_q), _p(out_k), _p(out_v),
-                                           _p(wq), _p(wk), _p(cos), _p(sin), B, S, H, int(head0), int(n_heads), Hn,
-                                           *_bshd_strides(x0), int(o_sp), int(o_sb), int(o_ss), int(o_sh),
-                                           int(s_rope), float(eps), dtype_code(x0.dtype)), "jenga_sp_qkv_prologue")
+    wq, wk = _norm_weight(wq, x0), _norm_weight(wk, x0)
+    cos, sin, s_rope = _rope_tables(cos, sin, s_rope, S)
+    _launch("jenga_sp_qkv_prologue", x0.device, _p(xq), _p(xk), _p(xv), _p(out_q), _p(out_k), _p(out_v), _p(wq), _p(wk),
+            _p(cos), _p(sin), B, S, H, int(head0), int(n_heads), Hn, *_bshd_strides(x0), int(o_sp), int(o_sb), int(o_ss),
+            int(o_sh), int(s_rope), float(eps), dtype_code(x0.dtype))
     return out_q, out_k, out_v
 
 
@@ -389,10 +473,8 @@ def rmsnorm_rows(x, weight, eps):
     w32 = weight.dtype == torch.float32
     w = weight.to(device=x.device).contiguous() if w32 else weight.to(device=x.device, dtype=x.dtype).contiguous()
     out = torch.empty(x2.shape, dtype=torch.float32 if w32 else x.dtype, device=x.device)
-    with _on(x.device):
-        _check(lib().jenga_rmsnorm_rows(_stream(x.device), _p(x2), _p(out), _p(w), x2.shape[0], C, x2.stride(0),
-                                        out.stride(0), float(eps), dtype_code(x.dtype), int(w32)),
-               "jenga_rmsnorm_rows")
+    _launch("jenga_rmsnorm_rows", x.device, _p(x2), _p(out), _p(w), x2.shape[0], C, x2.stride(0), out.stride(0), float(eps),
+            dtype_code(x.dtype), int(w32))
     return out.reshape(x.shape)
 
 
@@ -408,10 +490,8 @@ def rope_complex(x, cos64, sin64, s_rope, out_dtype=torch.float32):
     if x.stride(-1) != 1:
         x = x.contiguous()
     out = torch.empty((B, S, H, D), dtype=out_dtype, device=x.device)
-    with _on(x.device):
-        _check(lib().jenga_rope_complex(_stream(x.device), _p(x), _p(out), _p(cos64.contiguous()),
-                                        _p(sin64.contiguous()), B, S, H, *_bshd_strides(x), *_bshd_strides(out),
-                                        int(s_rope), codes[x.dtype], codes[out_dtype]), "jenga_rope_complex")
+    _launch("jenga_rope_complex", x.device, _p(x), _p(out), _p(cos64.contiguous()), _p(sin64.contiguous()), B, S, H,
+            *_bshd_strides(x), *_bshd_strides(out), int(s_rope), codes[x.dtype], codes[out_dtype])
     return out
 
 
@@ -441,10 +521,8 @@ def wan_norm_rope(x, weight, cos64, sin64, s_rope, eps, out=None):
         cos64, sin64 = cos64.contiguous(), sin64.contiguous()
     else:
         s_rope = 0
-    with _on(x.device):
-        _check(lib().jenga_wan_norm_rope(_stream(x.device), _p(x2), _p(o2), _p(w), _p(cos64), _p(sin64), rows, C,
-                                         x2.stride(0), o2.stride(0), int(s_rope), float(eps), dtype_code(x.dtype)),
-               "jenga_wan_norm_rope")
+    _launch("jenga_wan_norm_rope", x.device, _p(x2), _p(o2), _p(w), _p(cos64), _p(sin64), rows, C, x2.stride(0), o2.stride(0),
+            int(s_rope), float(eps), dtype_code(x.dtype))
     return out
 
 
@@ -466,12 +544,11 @@ def ln_modulate(x, shift, scale, eps=1e-6, shift2=None, scale2=None, mask=None, 
     if out is None:
         out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
     o2, _, _, ors = _rows2d(out)
-    v = lambda t: None if t is None else t.reshape(-1).to(dtype=x.dtype).contiguous()
-    sh, sc, sh2, sc2 = v(shift), v(scale), v(shift2), v(scale2)
+    dt = x.dtype
+    sh, sc, sh2, sc2 = _flat(shift, dt), _flat(scale, dt), _flat(shift2, dt), _flat(scale2, dt)
     m = None if mask is None else mask.to(torch.uint8).contiguous()
-    with _on(x.device):
-        _check(lib().jenga_ln_modulate(_stream(x.device), _p(x2), _p(o2), _p(sh), _p(sc), _p(sh2), _p(sc2), _p(m),
-                                       rows, C, xrs, ors, float(eps), dtype_code(x.dtype)), "jenga_ln_modulate")
+    _launch("jenga_ln_modulate", x.device, _p(x2), _p(o2), _p(sh), _p(sc), _p(sh2), _p(sc2), _p(m), rows, C, xrs, ors,
+            float(eps), dtype_code(x.dtype))
     return out
 
 
@@ -484,11 +561,10 @@ def gate_residual(res, y, gate, gate2=None, mask=None, out=None):
         out = torch.empty(res.shape, dtype=res.dtype, device=res.device)
     o2, _, _, ors = _rows2d(out)
     g = gate.reshape(-1).to(dtype=res.dtype).contiguous()
-    g2 = None if gate2 is None else gate2.reshape(-1).to(dtype=res.dtype).contiguous()
+    g2 = _flat(gate2, res.dtype)
     m = None if mask is None else mask.to(torch.uint8).contiguous()
-    with _on(res.device):
-        _check(lib().jenga_gate_residual(_stream(res.device), _p(r2), _p(y2), _p(g), _p(g2), _p(m), _p(o2), rows, C,
-                                         rrs, yrs, ors, dtype_code(res.dtype)), "jenga_gate_residual")
+    _launch("jenga_gate_residual", res.device, _p(r2), _p(y2), _p(g), _p(g2), _p(m), _p(o2), rows, C, rrs, yrs, ors,
+            dtype_code(res.dtype))
     return out
 
 
@@ -499,16 +575,14 @@ def gelu_tanh(x, out=None):
     if out is None:
         out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
     o2, _, _, ors = _rows2d(out)
-    with _on(x.device):
-        _check(lib().jenga_gelu_tanh(_stream(x.device), _p(x2), _p(o2), rows, C, xrs, ors, dtype_code(x.dtype)),
-               "jenga_gelu_tanh")
+    _launch("jenga_gelu_tanh", x.device, _p(x2), _p(o2), rows, C, xrs, ors, dtype_code(x.dtype))
     return out
 
 
 ACT_NONE, ACT_GELU_TANH = 0, 1
 BIAS_F32 = 256     # OR-ed into jenga_linear's `act`: the bias vector is float32
 OUT_F32 = 512      # OR-ed into jenga_linear's `act`: res and out are float32
-_GEMM_WORKSPACE = __import__("collections").OrderedDict()
+_GEMM_WORKSPACE = collections.OrderedDict()
 _GEMM_WORKSPACE_MAX = 8         # scratch buffers kept per process (64 MiB each), least recently used evicted
 
 
@@ -561,41 +635,12 @@ def linear(x, weight, bias=None, act=ACT_NONE, gate=None, res=None, out=None):
     N = weight.shape[0]
     if weight.dim() != 2 or weight.shape[1] != K or weight.stride(1) != 1 or weight.dtype != x.dtype:
         raise ValueError("linear: weight must be [N, K] in the input dtype with contiguous rows")
-    # a float32 residual (or out) selects the fp32 C / D form (JENGA_OUT_F32: the Wan blocks' residual stream)
-    out32 = (res is not None and res.dtype == torch.float32) or (out is not None and out.dtype == torch.float32)
-    odt = torch.float32 if out32 else x.dtype
-    if out is None:
-        out = torch.empty(tuple(x.shape[:-1]) + (N,), dtype=odt, device=x.device)
-    o2, Mo, No, ors = _rows2d(out)
-    if Mo != M or No != N or out.dtype != odt:
-        raise ValueError("linear: out must be [..., N] with as many rows as x (float32 when the residual is float32)")
-    r2, rrs = None, 0
-    if res is not None:
-        r2, Mr, Nr, rrs = _rows2d(res)
-        if Mr != M or Nr != N or res.dtype != odt:
-            raise ValueError("linear: res must match out")
-    if out32:
-        if int(act) & 0xff:
-            raise ValueError("linear: the float32 residual form has no activation epilogue")
-        act = int(act) | OUT_F32
-    if bias is not None:
-        if bias.dtype == torch.float32:     # (the gated bias of proj / fc2 / linear2: kept unrounded)
-            act = int(act) | BIAS_F32
-            bias = bias.reshape(-1).contiguous()
-        else:
-            bias = bias.reshape(-1).to(dtype=x.dtype).contiguous()
-        if bias.numel() != N:
-            raise ValueError("linear: bias must have N entries")
-    g32 = None
-    if gate is not None:
-        g32 = gate.reshape(-1).to(dtype=torch.float32).contiguous()
-        if g32.numel() != N:
-            raise ValueError("linear: gate must have N entries")
+    if int(act) & 0xff and _out_f32(res, out):      # (with a 16-bit gate / res the C entry decides)
+        raise ValueError("linear: the float32 residual form has no activation epilogue")
+    bias, g32, r2, rrs, out, o2, ors, act = _gemm_epilogue("linear", x, M, N, x.dtype, bias, act, gate, res, out)
     ws = _gemm_workspace(x.device)
-    with _on(x.device):
-        _check(lib().jenga_linear(_stream(x.device), _p(x2), _p(weight), _p(bias), _p(r2), _p(g32), _p(o2), M, N, K, xrs,
-                                  weight.stride(0), rrs, ors, int(act), _p(ws), ws.numel(), dtype_code(x.dtype)),
-               "jenga_linear")
+    _launch("jenga_linear", x.device, _p(x2), _p(weight), _p(bias), _p(r2), _p(g32), _p(o2), M, N, K, xrs, weight.stride(0),
+            rrs, ors, act, _p(ws), ws.numel(), dtype_code(x.dtype))
     return out
 
 
@@ -613,9 +658,7 @@ def quant_fp8_rows(x, out=None):
     if out.dtype != torch.uint8 or ro != rows or Ko != K or ors % 16 or out.device != x.device:
         raise ValueError("quant_fp8_rows: out must be uint8 [..., K] on x's device with a row stride multiple of 16")
     scale = torch.empty(rows, dtype=torch.float32, device=x.device)
-    with _on(x.device):
-        _check(lib().jenga_quant_fp8_rows(_stream(x.device), _p(x2), _p(o2), _p(scale), rows, K, xrs, ors,
-                                          dtype_code(x.dtype)), "jenga_quant_fp8_rows")
+    _launch("jenga_quant_fp8_rows", x.device, _p(x2), _p(o2), _p(scale), rows, K, xrs, ors, dtype_code(x.dtype))
     return out, scale
 
 
@@ -634,39 +677,14 @@ def linear_fp8(x8, x_scale, w8, w_scale, bias=None, act=ACT_NONE, gate=None, res
         if s_.dtype != torch.float32 or s_.dim() != 1 or s_.numel() != n_ or not s_.is_contiguous() or s_.device != x8.device:
             raise ValueError(f"linear_fp8: {what} must be a contiguous float32 vector with one entry per row")
     code = dtype_code(dtype)
-    out32 = (res is not None and res.dtype == torch.float32) or (out is not None and out.dtype == torch.float32)
-    odt = torch.float32 if out32 else dtype
-    if int(act) & 0xff and (out32 or gate is not None or res is not None):
+    if int(act) & 0xff and (gate is not None or res is not None or _out_f32(res, out)):
         raise ValueError("linear_fp8: the activation epilogue cannot be combined with gate / residual / float32 output")
     _need_gpu(x8, "linear_fp8")
     _need_gpu(w8, "linear_fp8")
-    if out is None:
-        out = torch.empty(tuple(x8.shape[:-1]) + (N,), dtype=odt, device=x8.device)
-    o2, Mo, No, ors = _rows2d(out)
-    if Mo != M or No != N or out.dtype != odt or ors % 8:
-        raise ValueError("linear_fp8: out must be [..., N] in dtype (float32 when the residual is) with as many rows as x8")
-    r2, rrs = None, 0
-    if res is not None:
-        r2, Mr, Nr, rrs = _rows2d(res)
-        if Mr != M or Nr != N or res.dtype != odt or rrs % 8:
-            raise ValueError("linear_fp8: res must match out")
-    act = int(act) | (OUT_F32 if out32 else 0)
-    if bias is not None:
-        if bias.dtype == torch.float32:
-            act |= BIAS_F32
-            bias = bias.reshape(-1).contiguous()
-        else:
-            bias = bias.reshape(-1).to(dtype=dtype).contiguous()
-        if bias.numel() != N:
-            raise ValueError("linear_fp8: bias must have N entries")
-    g32 = None
-    if gate is not None:
-        g32 = gate.reshape(-1).to(dtype=torch.float32).contiguous()
-        if g32.numel() != N:
-            raise ValueError("linear_fp8: gate must have N entries")
-    with _on(x8.device):
-        _check(lib().jenga_linear_fp8(_stream(x8.device), _p(x2), _p(x_scale), _p(w8), _p(w_scale), _p(bias), _p(r2), _p(g32),
-                                      _p(o2), M, N, K, xrs, w8.stride(0), rrs, ors, act, code), "jenga_linear_fp8")
+    bias, g32, r2, rrs, out, o2, ors, act = _gemm_epilogue("linear_fp8", x8, M, N, dtype, bias, act, gate, res, out,
+                                                           stride_multiple=8)
+    _launch("jenga_linear_fp8", x8.device, _p(x2), _p(x_scale), _p(w8), _p(w_scale), _p(bias), _p(r2), _p(g32), _p(o2), M, N,
+            K, xrs, w8.stride(0), rrs, ors, act, code)
     return out
 
 
@@ -679,12 +697,10 @@ def wan_ln_modulate(x, weight=None, bias=None, shift=None, scale=None, eps=1e-6,
     x2, rows, C, xrs = _rows2d(x)
     out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
     o2, _, _, ors = _rows2d(out)
-    v = lambda t: None if t is None else t.reshape(-1).to(dtype=torch.float32).contiguous()
-    w, b, sh, sc = v(weight), v(bias), v(shift), v(scale)
-    with _on(x.device):
-        _check(lib().jenga_wan_ln_modulate(_stream(x.device), _p(x2), _p(o2), _p(w), _p(b), _p(sh), _p(sc), rows, C,
-                                           xrs, ors, float(eps), dtype_code(out_dtype), int(bool(round_ln))),
-               "jenga_wan_ln_modulate")
+    f32 = torch.float32
+    w, b, sh, sc = _flat(weight, f32), _flat(bias, f32), _flat(shift, f32), _flat(scale, f32)
+    _launch("jenga_wan_ln_modulate", x.device, _p(x2), _p(o2), _p(w), _p(b), _p(sh), _p(sc), rows, C, xrs, ors, float(eps),
+            dtype_code(out_dtype), int(bool(round_ln)))
     return out
 
 
@@ -698,10 +714,8 @@ def wan_gate_residual(x, y, gate=None, out=None):
     if out is None:
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     o2, _, _, ors = _rows2d(out)
-    g = None if gate is None else gate.reshape(-1).to(dtype=torch.float32).contiguous()
-    with _on(x.device):
-        _check(lib().jenga_wan_gate_residual(_stream(x.device), _p(x2), _p(y2), _p(g), _p(o2), rows, C, xrs, yrs, ors,
-                                             dtype_code(y.dtype)), "jenga_wan_gate_residual")
+    g = _flat(gate, torch.float32)
+    _launch("jenga_wan_gate_residual", x.device, _p(x2), _p(y2), _p(g), _p(o2), rows, C, xrs, yrs, ors, dtype_code(y.dtype))
     return out
 
 
@@ -712,9 +726,7 @@ def block_pool(x, n_blocks):
     if D != 128 or n_blocks * 128 > S:
         raise ValueError("block_pool: head_dim must be 128 and n_blocks*128 <= S")
     out = torch.empty((B, H, n_blocks, 128), dtype=x.dtype, device=x.device)
-    with _on(x.device):
-        _check(lib().jenga_block_pool(_stream(x.device), _p(x), _p(out), B, H, n_blocks, *_bshd_strides(x),
-                                      dtype_code(x.dtype)), "jenga_block_pool")
+    _launch("jenga_block_pool", x.device, _p(x), _p(out), B, H, n_blocks, *_bshd_strides(x), dtype_code(x.dtype))
     return out
 
 
@@ -741,13 +753,10 @@ def block_select(qpool, kpool, neighbors, nk_img, text_blocks, top_k, p, first_f
             neighbors = neighbors.view(torch.uint8)
         neighbors = neighbors.to(dev).contiguous()
         nbr, nbc = neighbors.shape
-    with _on(dev):
-        _check(lib().jenga_block_select(_stream(dev), _p(qpool.contiguous()), _p(kpool.contiguous()), _p(neighbors),
-                                        nbr, nbc, _p(mask), _p(idx), _p(cnt), B, H, nq, nk_img, text_blocks,
-                                        int(top_k), float(p), int(first_frame_blocks), dtype_code(qpool.dtype),
-                                        int(SELECT_DEFAULT_FLAGS if flags is None else flags) |
-                                        (0 if head_dim == 128 else (head_dim << 8))),
-               "jenga_block_select")
+    _launch("jenga_block_select", dev, _p(qpool.contiguous()), _p(kpool.contiguous()), _p(neighbors), nbr, nbc, _p(mask),
+            _p(idx), _p(cnt), B, H, nq, nk_img, text_blocks, int(top_k), float(p), int(first_frame_blocks),
+            dtype_code(qpool.dtype),
+            int(SELECT_DEFAULT_FLAGS if flags is None else flags) | (0 if head_dim == 128 else (head_dim << 8)))
     return mask, idx, cnt
 
 
@@ -764,9 +773,8 @@ def pack_v(v, n_blocks=None, out=None, dst_block0=0, dst_blocks_total=None):
         dst_blocks_total = n_blocks if out is None else out.shape[2] // 2
     if out is None:
         out = torch.empty((B, H, dst_blocks_total * 2, 128, 64), dtype=v.dtype, device=v.device)
-    with _on(v.device):
-        _check(lib().jenga_pack_v(_stream(v.device), _p(v), _p(out), B, H, n_blocks, *_bshd_strides(v),
-                                  dst_block0, dst_blocks_total, dtype_code(v.dtype)), "jenga_pack_v")
+    _launch("jenga_pack_v", v.device, _p(v), _p(out), B, H, n_blocks, *_bshd_strides(v), dst_block0, dst_blocks_total,
+            dtype_code(v.dtype))
     return out
 
 
@@ -781,29 +789,20 @@ def bsattn_fwd(q, k, vt, seqlens, idx, cnt, nq_img, sm_scale, text_amp, text_blo
     n_blocks = S // 128
     if out is None:
         out = torch.empty((B, S, H, 128), dtype=q.dtype, device=q.device)
-    if seqlens is not None and (seqlens.dtype != torch.int32 or seqlens.device != q.device):
-        seqlens = seqlens.to(device=q.device, dtype=torch.int32)
-    if seqlens is not None and seqlens.numel() < B:
-        # the reference passes cu_seqlens_q[1:2] whatever the batch (attention_block_triton_diffres.py:327-329) and its
-        # kernel then reads past it for B > 1; here that is an error instead of an out-of-bounds read
-        raise ValueError(f"bsattn_fwd: seqlens has {seqlens.numel()} entries for batch {B}")
-    if idx is not None and idx.shape[-1] != n_blocks:
+    if idx is not None and idx.shape[-1] != n_blocks:       # (also without image query blocks, where nothing reads idx)
         raise ValueError("idx row length must equal the number of kv blocks")
+    seqlens = _attn_lists("bsattn_fwd", q.device, B, H, n_blocks, nq_img, seqlens, idx, cnt)
     if k.shape != q.shape or out.shape != q.shape:
         raise ValueError("bsattn_fwd: q, k and out must have the same [B,S,H,128] shape")
     if tuple(vt.shape) != (B, H, 2 * n_blocks, 128, 64) or not vt.is_contiguous() or vt.dtype != q.dtype:
         raise ValueError(f"bsattn_fwd: vt must be the contiguous pack_v workspace {(B, H, 2 * n_blocks, 128, 64)}")
-    if nq_img > 0 and (idx is None or cnt is None or tuple(idx.shape[:3]) != (B, H, nq_img)
-                       or tuple(cnt.shape) != (B, H, nq_img) or idx.dtype != torch.int32 or cnt.dtype != torch.int32
-                       or not idx.is_contiguous() or not cnt.is_contiguous()):
-        raise ValueError("bsattn_fwd: idx / cnt must be contiguous int32 [B,H,nq_img,n_blocks] / [B,H,nq_img]")
     fl = ATTN_DEFAULT_FLAGS if flags is None else flags
     if not xcd_remap:
         fl &= ~ATTN_XCD_REMAP
     pair = bool(fl & ATTN_PAIR)
     if pair and order is not None:
         # `order` ranks query BLOCKS; the pair kernel launches block PAIRS in an order of its own (ATTN_SORTED) -- dropping a
-        # caller's hint silently would misreport what ran (ADVICE r5)
+        # caller's hint silently would misreport what ran
         raise ValueError("bsattn_fwd: a launch-order hint (order=) cannot be combined with the pair kernel (ATTN_PAIR)")
     prof = ATTN_PROFILE
     with _on(q.device):
@@ -828,29 +827,18 @@ def bsattn_fwd(q, k, vt, seqlens, idx, cnt, nq_img, sm_scale, text_amp, text_blo
         if order_t is not None and (tuple(order_t.shape) != (B, H, nq_img) or order_t.dtype != torch.int32
                                     or not order_t.is_contiguous() or order_t.device != q.device):
             raise ValueError("bsattn_fwd: order must be a contiguous int32 [B,H,nq_img] tensor on the device")
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
+        e0 = _profile_start() if prof is not None else None
         common = (B, H, n_blocks, nq_img, *_bshd_strides(q), *_bshd_strides(k), *_bshd_strides(out), float(sm_scale),
                   float(text_amp), int(text_block_start), dtype_code(q.dtype))
         cflags = fl & (ATTN_XCD_REMAP | ATTN_BALANCE | ATTN_LP)
         if not pair:
-            _check(lib().jenga_bsattn_fwd(_stream(q.device), _p(q), _p(k), _p(vt), _p(out), _p(seqlens), _p(idx),
-                                          _p(cnt), _p(order_t), *common, cflags), "jenga_bsattn_fwd")
+            _enqueue("jenga_bsattn_fwd", q.device, _p(q), _p(k), _p(vt), _p(out), _p(seqlens), _p(idx), _p(cnt), _p(order_t),
+                     *common, cflags)
         else:
-            _check(lib().jenga_bsattn_pair_fwd(_stream(q.device), _p(q), _p(k), _p(vt), _p(out), _p(seqlens),
-                                               _p(pidx), _p(pcnt), _p(porder), *common, cflags & ~ATTN_LP),
-                   "jenga_bsattn_pair_fwd")
+            _enqueue("jenga_bsattn_pair_fwd", q.device, _p(q), _p(k), _p(vt), _p(out), _p(seqlens), _p(pidx), _p(pcnt),
+                     _p(porder), *common, cflags & ~ATTN_LP)
         if prof is not None:
-            e1.record()
-            prof.events.append((e0, e1))
-            prof.launches += 1
-            pairs = B * H * (n_blocks - nq_img) * n_blocks
-            tot = (cnt.sum(dtype=torch.int64) if cnt is not None else 0) + pairs
-            prof.pairs = tot if prof.pairs is None else prof.pairs + tot
-            prof.per_launch.append((prof.tag, tot))
-            if idx is not None and nq_img > 1:
-                prof.last_lists = (idx, cnt)
+            _profile_stop(prof, e0, B, H, n_blocks, nq_img, idx, cnt)
     return out
 
 
@@ -867,9 +855,8 @@ def quant_fp8_blocks(x, offset=None):
         raise ValueError("quant_fp8_blocks: offset must be a contiguous float32 [B,H,128] tensor on x's device")
     x8 = torch.empty((B, S, H, 128), dtype=torch.uint8, device=x.device)
     scale = torch.empty((B, H, S // 128), dtype=torch.float32, device=x.device)
-    with _on(x.device):
-        _check(lib().jenga_quant_fp8_blocks(_stream(x.device), _p(x), _p(x8), _p(scale), _p(offset), B, H, S // 128,
-                                            *_bshd_strides(x), dtype_code(x.dtype)), "jenga_quant_fp8_blocks")
+    _launch("jenga_quant_fp8_blocks", x.device, _p(x), _p(x8), _p(scale), _p(offset), B, H, S // 128, *_bshd_strides(x),
+            dtype_code(x.dtype))
     return x8, scale
 
 
@@ -893,36 +880,15 @@ def bsattn_fp8_fwd(q8, q_scale, k8, k_scale, vt, seqlens, idx, cnt, nq_img, sm_s
         out = torch.empty((B, S, H, 128), dtype=vt.dtype, device=q8.device)
     elif out.shape != q8.shape or out.dtype != vt.dtype or out.device != q8.device:
         raise ValueError("bsattn_fp8_fwd: out must be [B,S,H,128] in vt's dtype")
-    if seqlens is not None and (seqlens.dtype != torch.int32 or seqlens.device != q8.device):
-        seqlens = seqlens.to(device=q8.device, dtype=torch.int32)
-    if seqlens is not None and seqlens.numel() < B:
-        raise ValueError(f"bsattn_fp8_fwd: seqlens has {seqlens.numel()} entries for batch {B}")
-    if not 0 <= nq_img <= n_blocks:
-        raise ValueError("bsattn_fp8_fwd: nq_img must lie in [0, n_blocks]")
-    if nq_img > 0 and (idx is None or cnt is None or tuple(idx.shape) != (B, H, nq_img, n_blocks)
-                       or tuple(cnt.shape) != (B, H, nq_img) or idx.dtype != torch.int32 or cnt.dtype != torch.int32
-                       or not idx.is_contiguous() or not cnt.is_contiguous() or idx.device != q8.device
-                       or cnt.device != q8.device):
-        raise ValueError("bsattn_fp8_fwd: idx / cnt must be contiguous int32 [B,H,nq_img,n_blocks] / [B,H,nq_img]")
+    seqlens = _attn_lists("bsattn_fp8_fwd", q8.device, B, H, n_blocks, nq_img, seqlens, idx, cnt)
     prof = ATTN_PROFILE
     with _on(q8.device):
+        e0 = _profile_start() if prof is not None else None
+        _enqueue("jenga_bsattn_fp8_fwd", q8.device, _p(q8), _p(q_scale), _p(k8), _p(k_scale), _p(vt), _p(out), _p(seqlens),
+                 _p(idx), _p(cnt), B, H, n_blocks, nq_img, *_bshd_strides(q8), *_bshd_strides(k8), *_bshd_strides(out),
+                 float(sm_scale), float(text_amp), int(text_block_start), dt, ATTN_XCD_REMAP if xcd_remap else 0)
         if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _check(lib().jenga_bsattn_fp8_fwd(_stream(q8.device), _p(q8), _p(q_scale), _p(k8), _p(k_scale), _p(vt), _p(out),
-                                          _p(seqlens), _p(idx), _p(cnt), B, H, n_blocks, nq_img, *_bshd_strides(q8),
-                                          *_bshd_strides(k8), *_bshd_strides(out), float(sm_scale), float(text_amp),
-                                          int(text_block_start), dt, ATTN_XCD_REMAP if xcd_remap else 0),
-               "jenga_bsattn_fp8_fwd")
-        if prof is not None:
-            e1.record()
-            prof.events.append((e0, e1))
-            prof.launches += 1
-            tot = (cnt.sum(dtype=torch.int64) if cnt is not None else 0) + B * H * (n_blocks - nq_img) * n_blocks
-            prof.pairs = tot if prof.pairs is None else prof.pairs + tot
-            prof.per_launch.append((prof.tag, tot))
-            if idx is not None and nq_img > 1:
-                prof.last_lists = (idx, cnt)
+            _profile_stop(prof, e0, B, H, n_blocks, nq_img, idx, cnt)
     return out
 
 
@@ -934,9 +900,7 @@ def block_pool_d64(x, n_blocks):
         raise ValueError("block_pool_d64: x must be [B,S,H,64] with n_blocks*128 <= S")
     B, S, H, _ = x.shape
     out = torch.empty((B, H, n_blocks, 128), dtype=x.dtype, device=x.device)
-    with _on(x.device):
-        _check(lib().jenga_block_pool_d64(_stream(x.device), _p(x), _p(out), B, H, n_blocks, *_bshd_strides(x),
-                                          dtype_code(x.dtype)), "jenga_block_pool_d64")
+    _launch("jenga_block_pool_d64", x.device, _p(x), _p(out), B, H, n_blocks, *_bshd_strides(x), dtype_code(x.dtype))
     return out
 
 
@@ -953,23 +917,11 @@ def bsattn_d64_fwd(q, k, v, seqlens, idx, cnt, nq_img, sm_scale, text_amp, text_
     for name, t in (("k", k), ("v", v), ("out", out)):
         if t.shape != q.shape or t.dtype != q.dtype or t.device != q.device:
             raise ValueError(f"bsattn_d64_fwd: {name} must have q's shape, dtype and device")
-    if seqlens is not None and (seqlens.dtype != torch.int32 or seqlens.device != q.device):
-        seqlens = seqlens.to(device=q.device, dtype=torch.int32)
-    if seqlens is not None and seqlens.numel() < B:
-        raise ValueError(f"bsattn_d64_fwd: seqlens has {seqlens.numel()} entries for batch {B}")
-    if not 0 <= nq_img <= n_blocks:
-        raise ValueError("bsattn_d64_fwd: nq_img must lie in [0, n_blocks]")
-    if nq_img > 0 and (idx is None or cnt is None or tuple(idx.shape) != (B, H, nq_img, n_blocks)
-                       or tuple(cnt.shape) != (B, H, nq_img) or idx.dtype != torch.int32 or cnt.dtype != torch.int32
-                       or not idx.is_contiguous() or not cnt.is_contiguous() or idx.device != q.device
-                       or cnt.device != q.device):
-        raise ValueError("bsattn_d64_fwd: idx / cnt must be contiguous int32 [B,H,nq_img,n_blocks] / [B,H,nq_img]")
-    with _on(q.device):
-        _check(lib().jenga_bsattn_d64_fwd(_stream(q.device), _p(q), _p(k), _p(v), _p(out), _p(seqlens), _p(idx), _p(cnt),
-                                          B, H, n_blocks, nq_img, *_bshd_strides(q), *_bshd_strides(k), *_bshd_strides(v),
-                                          *_bshd_strides(out), float(sm_scale), float(text_amp), int(text_block_start),
-                                          dtype_code(q.dtype), ATTN_XCD_REMAP if xcd_remap else 0),
-               "jenga_bsattn_d64_fwd")
+    seqlens = _attn_lists("bsattn_d64_fwd", q.device, B, H, n_blocks, nq_img, seqlens, idx, cnt)
+    # (does not record into ATTN_PROFILE)
+    _launch("jenga_bsattn_d64_fwd", q.device, _p(q), _p(k), _p(v), _p(out), _p(seqlens), _p(idx), _p(cnt), B, H, n_blocks,
+            nq_img, *_bshd_strides(q), *_bshd_strides(k), *_bshd_strides(v), *_bshd_strides(out), float(sm_scale),
+            float(text_amp), int(text_block_start), dtype_code(q.dtype), ATTN_XCD_REMAP if xcd_remap else 0)
     return out
 
 
@@ -988,11 +940,9 @@ def cross_attn_fwd(q, k, v, sm_scale=None, out=None, kv_len=None):
     if out is None:
         out = torch.empty((B, Sq, H, 128), dtype=q.dtype, device=q.device)
     vt = pack_v(v, Skv // 128)
-    with _on(q.device):
-        _check(lib().jenga_cross_attn_fwd(_stream(q.device), _p(q), _p(k), _p(vt), _p(out), B, H, Sq // 128, Skv // 128,
-                                          kv_len, *_bshd_strides(q), *_bshd_strides(k), *_bshd_strides(out),
-                                          float(D ** -0.5 if sm_scale is None else sm_scale), dtype_code(q.dtype)),
-               "jenga_cross_attn_fwd")
+    _launch("jenga_cross_attn_fwd", q.device, _p(q), _p(k), _p(vt), _p(out), B, H, Sq // 128, Skv // 128, kv_len,
+            *_bshd_strides(q), *_bshd_strides(k), *_bshd_strides(out), float(D ** -0.5 if sm_scale is None else sm_scale),
+            dtype_code(q.dtype))
     return out
 
 
@@ -1019,12 +969,10 @@ def dense_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_kv=None, sm_scale=None, o
     elif out.shape != q.shape or out.dtype != q.dtype or out.stride(2) != 1 or out.device != q.device:
         raise ValueError("dense_varlen_fwd: out must match q (unit head_dim stride)")
     Tq, H, D = q.shape
-    with _on(q.device):
-        _check(lib().jenga_dense_varlen_fwd(_stream(q.device), _p(q), _p(k), _p(v), _p(out), _p(cu_seqlens_q),
-                                            _p(cu_seqlens_kv), cu_seqlens_q.numel() - 1, Tq, k.shape[0], H, q.stride(0),
-                                            q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0),
-                                            out.stride(1), float(D ** -0.5 if sm_scale is None else sm_scale),
-                                            dtype_code(q.dtype)), "jenga_dense_varlen_fwd")
+    _launch("jenga_dense_varlen_fwd", q.device, _p(q), _p(k), _p(v), _p(out), _p(cu_seqlens_q), _p(cu_seqlens_kv),
+            cu_seqlens_q.numel() - 1, Tq, k.shape[0], H, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0),
+            v.stride(1), out.stride(0), out.stride(1), float(D ** -0.5 if sm_scale is None else sm_scale),
+            dtype_code(q.dtype))
     return out
 
 
@@ -1036,9 +984,7 @@ def order_by_count(cnt, segment):
         raise ValueError("order_by_count: cnt must be a contiguous int32 [B,H,nq] tensor")
     B, H, nq = cnt.shape
     order = torch.empty_like(cnt)
-    with _on(cnt.device):
-        _check(lib().jenga_order_by_count(_stream(cnt.device), _p(cnt), B * H, nq, int(segment), _p(order)),
-               "jenga_order_by_count")
+    _launch("jenga_order_by_count", cnt.device, _p(cnt), B * H, nq, int(segment), _p(order))
     return order
 
 
@@ -1053,9 +999,7 @@ def pair_merge(idx, cnt, n_blocks):
     npair = (nq + 1) // 2
     pidx = torch.empty((B, H, npair, nb), dtype=torch.int32, device=idx.device)
     pcnt = torch.empty((B, H, npair, 4), dtype=torch.int32, device=idx.device)
-    with _on(idx.device):
-        _check(lib().jenga_pair_merge(_stream(idx.device), _p(idx.contiguous()), _p(cnt.contiguous()), B, H, nq, nb,
-                                      _p(pidx), _p(pcnt)), "jenga_pair_merge")
+    _launch("jenga_pair_merge", idx.device, _p(idx.contiguous()), _p(cnt.contiguous()), B, H, nq, nb, _p(pidx), _p(pcnt))
     return pidx, pcnt
 
 
@@ -1065,9 +1009,7 @@ def ulysses_pack_heads(x, n_ranks, out=None):
     B, S, H, D = x.shape
     if out is None:
         out = torch.empty((n_ranks, B, S, H // n_ranks, D), dtype=x.dtype, device=x.device)
-    with _on(x.device):
-        _check(lib().jenga_ulysses_pack_heads(_stream(x.device), _p(x), _p(out), B, S, H, n_ranks,
-                                              *_bshd_strides(x)), "jenga_ulysses_pack_heads")
+    _launch("jenga_ulysses_pack_heads", x.device, _p(x), _p(out), B, S, H, n_ranks, *_bshd_strides(x))
     return out
 
 
@@ -1077,7 +1019,5 @@ def ulysses_unpack_heads(recv, n_ranks, out=None):
     N, B, S, Hn, D = recv.shape
     if out is None:
         out = torch.empty((B, S, Hn * N, D), dtype=recv.dtype, device=recv.device)
-    with _on(recv.device):
-        _check(lib().jenga_ulysses_unpack_heads(_stream(recv.device), _p(recv.contiguous()), _p(out), B, S, Hn * N, N,
-                                                *_bshd_strides(out)), "jenga_ulysses_unpack_heads")
+    _launch("jenga_ulysses_unpack_heads", recv.device, _p(recv.contiguous()), _p(out), B, S, Hn * N, N, *_bshd_strides(out))
     return out

@@ -60,6 +60,14 @@ def _check_narrow_heads(narrow_heads, head_dim, qk_dtype):
         raise ValueError("jenga_amd: narrow_heads='native' cannot be combined with qk_dtype='fp8'")
 
 
+def _pooled_for(qk_dtype, q, k, nimg, nb, pooled=None):
+    """The (qpool, kpool) the selection runs on.  FP8 needs the block means of k whether the caller has them or not (they
+    give K's smoothing offset): pooled here, once, they serve the selection too.  Otherwise the caller's, or None."""
+    if qk_dtype == "fp8" and pooled is None:
+        pooled = (_capi.block_pool(q, nimg) if nimg > 0 else None, _capi.block_pool(k, nb))
+    return pooled
+
+
 def _attend_fp8(q, k, vt, kpool, seqlens, idx, cnt, nimg, text_amp, out=None):
     """The FP8 Q.K path behind the (unchanged) selection: q and k quantised per 128-token block, K after subtracting its
     mean over the sequence -- the mean of the block means the selection already has, so no further pass over K."""
@@ -78,8 +86,7 @@ def attencarve_packed(q, k, vt, top_k, seqlens, text_blocks, text_amp, prob_thre
     _check_qk_dtype(qk_dtype, D)
     nb = S // BLOCK
     nimg = nb - text_blocks
-    if qk_dtype == "fp8" and pooled is None:
-        pooled = (_capi.block_pool(q, nimg) if nimg > 0 else None, _capi.block_pool(k, nb))
+    pooled = _pooled_for(qk_dtype, q, k, nimg, nb, pooled)
     idx = cnt = None
     if nimg > 0:
         _, idx, cnt = build_block_index(q, k, top_k, text_blocks, prob_threshold, block_neighbor_list,
@@ -120,29 +127,22 @@ def _combined(query, key, value, top_k, seqlens, text_blocks, text_amp, prob_thr
                                                 block_neighbor_list, nimg, text_blocks, top_k, prob_threshold,
                                                 first_frame_blocks=first_frame_blocks, want_mask=return_mask, head_dim=64)
         out = _capi.bsattn_d64_fwd(query, key, value, seqlens, idx, cnt, nimg, 64 ** -0.5, text_amp, nimg)
-        if context_size is not None and context_size != S:
-            out = out[:, :context_size]
-        if not shape_xfuse:
-            out = out.reshape(B, out.shape[1], H * D)
-        return (out, mask) if return_mask else out
-    pooled = None
-    if qk_dtype == "fp8":
-        pooled = (_capi.block_pool(query, nimg) if nimg > 0 else None, _capi.block_pool(key, nb))
-    if nimg > 0:
-        mask, idx, cnt = build_block_index(query, key, top_k, text_blocks, prob_threshold, block_neighbor_list,
-                                           first_frame_blocks, want_mask=return_mask, pooled=pooled, head_dim=head_dim)
-    vt = _capi.pack_v(value, nb)
-    if qk_dtype == "fp8":
-        out = _attend_fp8(query, key, vt, pooled[1], seqlens, idx, cnt, nimg, text_amp)
     else:
-        out = _capi.bsattn_fwd(query, key, vt, seqlens, idx, cnt, nimg, head_dim ** -0.5, text_amp, nimg)
+        pooled = _pooled_for(qk_dtype, query, key, nimg, nb)
+        if nimg > 0:
+            mask, idx, cnt = build_block_index(query, key, top_k, text_blocks, prob_threshold, block_neighbor_list,
+                                               first_frame_blocks, want_mask=return_mask, pooled=pooled, head_dim=head_dim)
+        vt = _capi.pack_v(value, nb)
+        if qk_dtype == "fp8":
+            out = _attend_fp8(query, key, vt, pooled[1], seqlens, idx, cnt, nimg, text_amp)
+        else:
+            out = _capi.bsattn_fwd(query, key, vt, seqlens, idx, cnt, nimg, head_dim ** -0.5, text_amp, nimg)
     if context_size is not None and context_size != S:
         out = out[:, :context_size]
-    if head_dim != 128:
+    if D != head_dim:           # the padded channels
         out = out[..., :head_dim].contiguous()
-        D = head_dim
     if not shape_xfuse:
-        out = out.reshape(B, out.shape[1], H * D)
+        out = out.reshape(B, out.shape[1], H * head_dim)
     return (out, mask) if return_mask else out
 
 

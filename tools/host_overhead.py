@@ -36,11 +36,19 @@ def main():
     wn = torch.ones(128, device=dev, dtype=bf)
     q = torch.empty(1, 128, 24, 128, device=dev, dtype=bf)
     k = torch.empty_like(q)
+    # block-sparse attention at S = 256: one image block (keeps both kv blocks) and one text block, 2 heads
+    aq = torch.randn(1, 256, 2, 128, device=dev, dtype=bf)
+    avt = _capi.pack_v(aq, 2)
+    aidx = torch.tensor([0, 1], dtype=torch.int32, device=dev).expand(1, 2, 1, 2).contiguous()
+    acnt = torch.full((1, 2, 1), 2, dtype=torch.int32, device=dev)
+    alen = torch.tensor([256], dtype=torch.int32, device=dev)
     out = {
         "torch.nn.functional.linear": per_call(lambda: torch.nn.functional.linear(x, w, b)),
         "_capi.linear (bias)": per_call(lambda: _capi.linear(x, w, b)),
         "_capi.linear (gate + residual)": per_call(lambda: _capi.linear(x, w, b, gate=vec, res=x)),
         "_capi.ln_modulate": per_call(lambda: _capi.ln_modulate(x, vec, vec)),
+        "_capi.gate_residual": per_call(lambda: _capi.gate_residual(x, x, vec)),
+        "_capi.bsattn_fwd (S=256)": per_call(lambda: _capi.bsattn_fwd(aq, aq, avt, alen, aidx, acnt, 1, 128 ** -0.5, 0.0, 1)),
         "_capi.qk_norm_rope_pool": per_call(lambda: _capi.qk_norm_rope_pool(qkv[:, :, 0], qkv[:, :, 1], wn, wn, None, None, q, k)),
         "_capi.pack_v": per_call(lambda: _capi.pack_v(qkv[:, :, 2], 1)),
         "torch.empty": per_call(lambda: torch.empty((1, 128, 3072), dtype=bf, device=dev)),
